@@ -12,13 +12,20 @@ W (weak scaling; preset configs[4]: 8192 x 262144 rank 256 per GPU); H is replic
 its numerators (RCCL).  `value` is the whole-job algorithmic GFLOP/s (8 * rows * total_cols * rank flops per
 iteration); iterations/s is reported next to it.
 
-Timing: W warm-up steps, an untimed pre-roll (`preroll_steps`, ~0.4 s: the chip's clocks settle under load), then
-blocks of exactly K steps, each bracketed by barrier + synchronize, until two consecutive blocks agree within 2 %;
-the median of the settled blocks is reported and every block is listed.
+A plain run (`--steps K --warmup W`) measures the headline figure and nothing else: set-up, an untimed pre-roll
+(`preroll_steps`, ~0.4 s: the chip's clocks settle under load), the factors reset to their initial values, W warm-up
+steps, then ONE block of exactly K timed steps bracketed by barrier + synchronize (`ms_per_step` = block time / K).
+Every rank thus ends on the factors after exactly W + K iterations from the seeded inputs, whatever the speed of the
+build: `--dump-outputs DIR` writes them (W.npy, H.npy, float32; rank 0's shard when sharded; a fixed seeded sample of
+rows when they exceed 64 MB) so that two builds can be compared output for output.
+
+`--full` adds everything else, as before: the headline leg is timed as W warm-up steps, the pre-roll, then blocks of
+exactly K steps until two consecutive blocks agree within 2 % (the median of the settled blocks is reported and every
+block is listed), and the line carries the legs below.
 
 The headline leg runs in the 'f16' operand mode (fp16 operands and target, fp32 accumulation: bf16's MFMA rate, and the
-mode that meets the reference within 1e-4 -- checked in the same run, `parity`); the 'bf16' mode configs[1] names is
-timed next to it (`bf16_mode`).  Printed JSON also carries
+mode that meets the reference within 1e-4 -- checked in a --full run, `parity`); the 'bf16' mode configs[1] names is
+timed next to it (`bf16_mode`).  With --full, printed JSON also carries
   roofline      the fused kernel's achieved TFLOP/s (algorithmic flops per launch / mean launch time measured
                 live with hipEvents on the launching stream) against the dense bf16 MFMA peak, plus the same
                 launch expressed as HBM GB/s of algorithmic bytes;
@@ -61,7 +68,14 @@ def parse():
     ap.add_argument('--rows', type=int, default=None)
     ap.add_argument('--cols', type=int, default=None, help='columns PER GPU')
     ap.add_argument('--rank', type=int, default=None)
-    ap.add_argument('--repeats', type=int, default=5, help='minimum number of timed blocks of --steps steps each; blocks '
+    ap.add_argument('--full', action='store_true',
+                    help='everything besides the headline figure: repeated timed blocks, roofline / telemetry / ceiling legs, '
+                         'the other operand mode, CPU baseline and parity, beta sweep, NMFD / NMF2D, fit(), real-data mode, '
+                         'the reference notebook workload; multi-GPU: the same-shard 1-GPU denominator')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write the factors the timed path computed in its last step to DIR/W.npy and '
+                         'DIR/H.npy (float32, at most 64 MB in all: a fixed seeded sample of rows beyond that)')
+    ap.add_argument('--repeats', type=int, default=5, help='--full: minimum number of timed blocks of --steps steps each; blocks '
                     'are added (up to --max-repeats) until two consecutive ones agree within 2 %%; the median block is reported')
     ap.add_argument('--max-repeats', type=int, default=40)
     ap.add_argument('--preroll-s', type=float, default=0.4, help='untimed iterations before the first block, in seconds of '
@@ -90,8 +104,8 @@ def parse():
     ap.add_argument('--force-dist', action='store_true', help='run the sharded (all-reduce) path even at world size 1')
     ap.add_argument('--gram', action='store_true', help="--beta 2 only: time fit()'s path without reconstruction (X @ panel + Gram "
                     'matrix) instead of the 12*N*C*R kernel')
-    ap.add_argument('--ref-notebook', action='store_true', help="add the ref_notebook sub-object (the reference's own published "
-                    'workload, 5168x1025 rank 88, five betas) to a run that is not the default one')
+    ap.add_argument('--ref-notebook', action='store_true', help="--full: add the ref_notebook sub-object (the reference's own "
+                    'published workload, 5168x1025 rank 88, five betas) to a run that is not the default one')
     ap.add_argument('--telemetry-s', type=float, default=0.8, help='seconds of back-to-back iterations (untimed, after the '
                     'timed blocks) during which a side thread samples core clock and socket power through amdsmi; the means go '
                     'into roofline.clock_mhz / power_w (0 disables)')
@@ -103,6 +117,8 @@ def parse():
     a = ap.parse_args()
     if a.precision == 'auto' and a.workload not in ('nmfd', 'nmf2d', 'betamu'):
         ap.error("--precision auto: only for --workload nmfd / nmf2d / betamu (the dense workloads report 'auto' as real_data_mode)")
+    if a.dump_outputs and a.workload not in ('nmf', 'betamu'):
+        ap.error('--dump-outputs: the dense workloads only (nmf, betamu)')
     return a
 
 
@@ -371,6 +387,24 @@ def timed_blocks(run, steps, min_repeats, max_repeats, barrier=None, reduce_max=
             break
     tail = blocks[-max(1, min_repeats):]          # the settled end of the run
     return sorted(tail)[len(tail) // 2], blocks
+
+
+DUMP_BYTES_MAX = 64 * 10 ** 6 - 4096      # --dump-outputs: 64 MB in all, .npy headers included
+
+
+def dump_outputs(d, arrays):
+    """Write each factor as d/<name>.npy (float32).  When they hold more than DUMP_BYTES_MAX together, every one keeps the
+    same share of its rows, drawn by a fixed seed (sorted): the same rows in every run of the same shape."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    total = sum(t.numel() * 4 for t in arrays.values())
+    for name, t in arrays.items():
+        t = t.detach().float()
+        if total > DUMP_BYTES_MAX:
+            keep = max(1, int(t.shape[0] * DUMP_BYTES_MAX // total))
+            rows = torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            t = t[rows.to(t.device)]
+        np.save(os.path.join(d, name + '.npy'), t.cpu().numpy())
 
 
 def cpu_baseline(V, W0, H0, beta, iters, betamu=False):
@@ -667,8 +701,10 @@ def main_plca(a):
 
 def dense_leg(a, V, W0, H0, beta, precision, group, world, dev, want_roofline, betamu=False, blocks_min=None, telemetry=False,
               gram=False):
-    """W warm-up steps, an untimed pre-roll, then blocks of exactly K steps, each bracketed by barrier + synchronize; the
-    block time is the MAX over ranks, the reported ms/step the median of the settled blocks.  Returns a dict."""
+    """--full: W warm-up steps, an untimed pre-roll, then blocks of exactly K steps, each bracketed by barrier + synchronize;
+    the block time is the MAX over ranks, the reported ms/step the median of the settled blocks.  Plain run: the pre-roll,
+    the factors back to W0 / H0, W warm-up steps, one block of exactly K steps.  Returns a dict ('W', 'H': the factors
+    right after the timed steps)."""
     from torchnmf_amd.engine import DenseMU, KernelTimer
     N, C = V.shape
     R = W0.shape[1]
@@ -692,6 +728,7 @@ def dense_leg(a, V, W0, H0, beta, precision, group, world, dev, want_roofline, b
             trainer.step(closure)
         step()
         eng = next(iter(trainer._engines.values()))[0]
+        W, H = layer.W, layer.H
     else:
         eng = DenseMU(V, W, H, beta, precision=precision, group=group, block_rows=a.block_rows, allow_gram=gram)
         assert eng.gram_path == (gram and beta == 2 and not (precision == 'f16x' and R > 128))
@@ -700,8 +737,9 @@ def dense_leg(a, V, W0, H0, beta, precision, group, world, dev, want_roofline, b
             eng.w_step()
             eng.h_step()
     dev_sync()
-    for _ in range(a.warmup):
-        step()
+    if a.full:
+        for _ in range(a.warmup):
+            step()
     if world > 1:
         # every rank must run the SAME number of steps (each holds collectives): a fixed pre-roll instead of a timed one
         preroll = 60
@@ -710,6 +748,16 @@ def dense_leg(a, V, W0, H0, beta, precision, group, world, dev, want_roofline, b
         dev_sync()
     else:
         preroll = preroll_steps(step, a.preroll_s)
+    if not a.full:
+        # plain run: the pre-roll only settles the clocks; from W0 / H0 again, so that the timed steps end on the factors
+        # after exactly W + K iterations however many pre-roll steps this build managed (--dump-outputs)
+        with torch.no_grad():
+            W.copy_(W0)
+            H.copy_(H0)
+        if not betamu:
+            eng.refresh_images()          # (BetaMu re-derives its images by itself: the parameters' versions moved)
+        for _ in range(a.warmup):
+            step()
 
     def barrier():
         if world > 1:
@@ -724,11 +772,16 @@ def dense_leg(a, V, W0, H0, beta, precision, group, world, dev, want_roofline, b
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         return float(tt.item())
-    # (multi-rank: a fixed block count, so that every rank runs the same number of collectives)
-    ms, blocks = timed_blocks(step, a.steps, blocks_min or a.repeats, (blocks_min or a.repeats) if world > 1 else a.max_repeats,
-                              barrier, reduce_max)
+    if a.full:
+        # (multi-rank: a fixed block count, so that every rank runs the same number of collectives)
+        ms, blocks = timed_blocks(step, a.steps, blocks_min or a.repeats, (blocks_min or a.repeats) if world > 1 else a.max_repeats,
+                                  barrier, reduce_max)
+    else:
+        ms, blocks = timed_blocks(step, a.steps, 1, 1, barrier, reduce_max)     # one block of exactly K steps
     out = {'precision': precision, 'ms_per_step': ms, 'blocks_ms_per_step': [round(x, 4) for x in blocks],
            'preroll_steps': preroll, 'gflops': flops_per_iter_gpu * world / (ms * 1e-3) / 1e9, 'eng': eng}
+    if a.dump_outputs:
+        out['W'], out['H'] = W.detach().clone(), H.detach().clone()
     # ---- roofline leg: K more steps, right after the timed region, with hipEvents around every fused launch
     # (recording inside the timed region costs ~2 % and folds the dispatch gap in front of each kernel into its
     # span; these spans agree with the rocprofv3 kernel-trace durations)
@@ -1156,18 +1209,20 @@ def main():
     W0 = torch.randn(C, R, device=dev, generator=gw).abs_()            # the reference's init law (nmf.py:221)
     gh = torch.Generator(device=dev).manual_seed(3000)
     H0 = torch.randn(N, R, device=dev, generator=gh).abs_()            # replicated
-    do_cpu = rank == 0 and world == 1 and a.cpu_iters > 0
+    do_cpu = a.full and rank == 0 and world == 1 and a.cpu_iters > 0
     betamu = a.workload == 'betamu'
     flops_per_iter_gpu = (8.0 if beta == 1 else 12.0) * N * C * R
 
-    head = dense_leg(a, V, W0, H0, beta, a.precision, group, world, dev, not a.no_roofline, betamu, telemetry=True,
+    head = dense_leg(a, V, W0, H0, beta, a.precision, group, world, dev, a.full and not a.no_roofline, betamu, telemetry=True,
                      gram=a.gram and beta == 2 and world == 1)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {'W': head.pop('W'), 'H': head.pop('H')})
     # ---- N > 1: the 1-GPU denominator of THIS workload, measured in THIS run (the default N = 1 line is
     # configs[1] at rank 128, the N > 1 lines run configs[4]'s shard at rank 256 -- a curve through the default lines would
     # divide two different workloads).  Rank 0 times its own shard unsharded (no collective, the fused apply instead of
     # slab reduction + all-reduce + apply) while the other ranks wait at a barrier.
     same1 = None
-    if world > 1 and (group is not None):
+    if a.full and world > 1 and (group is not None):
         import torch.distributed as dist
         if rank == 0:
             one = dense_leg(a, V, W0, H0, beta, a.precision, None, 1, dev, False, blocks_min=3)
@@ -1183,7 +1238,7 @@ def main():
     # secondary, clearly labelled object: the other single-plane operand type, timed in the same run
     other = {'f16': 'bf16', 'bf16': 'f16'}.get(a.precision)
     second = None
-    if other and not betamu and not a.no_parity_mode and world == 1:
+    if a.full and other and not betamu and not a.no_parity_mode and world == 1:
         pm = dense_leg(a, V, W0, H0, beta, other, group, world, dev, not a.no_roofline)
         second = {'precision': other, 'dtype': DTYPE_LONG[other], 'value': round(pm['gflops'], 1), 'unit': 'GFLOP/s',
                   'iters_per_s': round(1e3 / pm['ms_per_step'], 2), 'ms_per_step': round(pm['ms_per_step'], 4),
@@ -1211,7 +1266,7 @@ def main():
     beta_sweep = None
     nmfd = None
     nmf2d = None
-    default_run = (world == 1 and not betamu and not a.no_sweep and beta == 1 and (N, C, R) == (4096, 65536, 128)
+    default_run = (a.full and world == 1 and not betamu and not a.no_sweep and beta == 1 and (N, C, R) == (4096, 65536, 128)
                    and a.precision in ('f16', 'bf16'))
     if default_run:
         from oracle import aten_port
@@ -1307,7 +1362,7 @@ def main():
         del Vr
 
     ref_nb = None
-    if default_run or a.ref_notebook:
+    if default_run or (a.full and a.ref_notebook):
         try:
             ref_nb = ref_notebook_leg(a, dev, do_cpu)
         except Exception as ex:              # (context leg: report the failure instead of losing the whole line)
@@ -1320,7 +1375,7 @@ def main():
             'metric': f'MU GFLOP/s (algorithmic {"8" if beta == 1 else "12"}*N*C*R per iteration), dense NMF '
                       f'{N}x{C} rank-{R} beta={beta:g}; MU iterations/s alongside',
             'value': round(head['gflops'], 1), 'unit': 'GFLOP/s', 'iters_per_s': round(1e3 / ms_per_step, 2),
-            'n_gpus': world, 'nranks': nranks, 'steps': a.steps, 'warmup': a.warmup, 'preroll_steps': head['preroll_steps'],
+            'n_gpus': world, 'nranks': nranks, 'steps': a.steps, 'warmup': a.warmup, 'full': a.full, 'preroll_steps': head['preroll_steps'],
             'ms_per_step': round(ms_per_step, 4),
             'repeats': len(head['blocks_ms_per_step']), 'blocks_ms_per_step': head['blocks_ms_per_step'],
             'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,

@@ -233,8 +233,8 @@ def test_bench_script_control_flow_world2(tmp_path):
     env = dict(os.environ)
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT'):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--standin', '--steps', '3', '--warmup', '1',
-                        '--repeats', '2', '--cpu-iters', '0', '--rows', '48', '--cols', '40', '--rank', '5'],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--standin', '--full', '--steps', '3',
+                        '--warmup', '1', '--repeats', '2', '--cpu-iters', '0', '--rows', '48', '--cols', '40', '--rank', '5'],
                        capture_output=True, text=True, timeout=600, env=env, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
@@ -249,3 +249,34 @@ def test_bench_script_control_flow_world2(tmp_path):
     s1 = d['same_shard_1gpu']
     assert s1['ms_per_step'] > 0 and d['efficiency'] == pytest.approx(s1['ms_per_step'] / d['ms_per_step'], rel=1e-3)
     assert 'another workload' in d['scaling_note']
+
+
+def _bench_plain(tmp_path, tag, *args):
+    import json
+    import subprocess
+    env = dict(os.environ)
+    for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT'):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--standin', '--rows', '48', '--cols', '40',
+                        '--rank', '5', '--dump-outputs', str(tmp_path / tag), *args],
+                       capture_output=True, text=True, timeout=600, env=env, cwd=str(tmp_path))
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1, r.stdout[-2000:]
+    return json.loads(lines[0]), {n: np.load(tmp_path / tag / f'{n}.npy') for n in ('W', 'H')}
+
+
+def test_bench_script_plain_run(tmp_path):
+    """A plain `bench.py --steps K --warmup W` (here over the CPU stand-in): ONE block of exactly K timed steps, none of the
+    --full legs, and --dump-outputs writes the factors after exactly W + K iterations from the seeded inputs -- the same
+    bits however long the pre-roll ran, other bits after another iteration count."""
+    d, a = _bench_plain(tmp_path, 'a', '--steps', '3', '--warmup', '2')
+    assert d['steps'] == 3 and d['warmup'] == 2 and d['full'] is False and 'NOT a measurement' in d['data']
+    assert d['repeats'] == 1 and len(d['blocks_ms_per_step']) == 1 and d['ms_per_step'] == d['blocks_ms_per_step'][0] > 0
+    assert d['unit'] == 'GFLOP/s' and d['higher_is_better'] is True and d['dtype'] == 'f16' and d['metric'].startswith('MU GFLOP/s')
+    assert all(d[k] is None for k in ('roofline', 'cpu_baseline', 'parity', 'bf16_mode', 'beta_sweep', 'nmfd', 'fit', 'ref_notebook'))
+    assert a['W'].shape == (40, 5) and a['H'].shape == (48, 5) and a['W'].dtype == a['H'].dtype == np.float32
+    _, b = _bench_plain(tmp_path, 'b', '--steps', '4', '--warmup', '1', '--preroll-s', '0')     # 5 iterations again
+    assert all(np.array_equal(a[n], b[n]) for n in a)
+    _, c = _bench_plain(tmp_path, 'c', '--steps', '4', '--warmup', '2')                         # 6 iterations
+    assert not np.array_equal(a['W'], c['W'])

@@ -191,13 +191,18 @@ def test_g7_betamu_oracle(case):
 @pytest.mark.parametrize('beta', [-1, 0, 0.5, 1, 1.5, 2, 3])
 @pytest.mark.parametrize('pen', ['plain', 'pen'])
 def test_g7_aten_port_is_bit_identical(beta, pen):
-    """The CPU-baseline port of BetaMu (bench.py --workload betamu) reproduces the reference bit for bit."""
+    """The CPU-baseline port of BetaMu (bench.py --workload betamu) reproduces the reference bit for bit.  The reference's
+    own last bits follow the host's sgemm kernels, so the port must equal one recorded run of the reference exactly: g7's
+    host or one of g7_betamu_hosts (tools/make_golden.py g7_hosts)."""
     from oracle import aten_port
     torch.set_num_threads(1)
     g = load_golden('g7_betamu')
+    hosts = load_golden('g7_betamu_hosts')
     V, W0, H0 = (torch.from_numpy(g[k]) for k in ('V', 'W0', 'H0'))
     W, H = aten_port.betamu_iterations(V, W0, H0, beta, 5, *G7_PEN[pen])
-    assert np.array_equal(W.numpy(), g[f'b{beta}_{pen}_both_W5']) and np.array_equal(H.numpy(), g[f'b{beta}_{pen}_both_H5'])
+    key = f'b{beta}_{pen}_both'
+    runs = [(g[f'{key}_W5'], g[f'{key}_H5'])] + [(hosts[f'h{i}_{key}_W5'], hosts[f'h{i}_{key}_H5']) for i in range(len(hosts['hosts']))]
+    assert any(np.array_equal(W.numpy(), Wr) and np.array_equal(H.numpy(), Hr) for Wr, Hr in runs)
 
 
 # ---- NMF2D / NMF3D (SURVEY.md section 8 row f2) ------------------------------------------------------------------

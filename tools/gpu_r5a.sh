@@ -5,7 +5,7 @@ TAG=${1:-r5a}; OUT=gpurun_out/$TAG; mkdir -p $OUT
 timeout 1500 python -m pytest tests -q -m gpu > $OUT/pytest_gpu.log 2>&1; echo "pytest rc=$?"; tail -15 $OUT/pytest_gpu.log | cut -c1-300
 for i in 1 2; do
   for m in 1 0; do
-    TORCHNMF_AMD_NMFD_WINSTAGE=$m timeout 300 python bench.py --workload nmfd --cpu-iters 0 --steps 50 --telemetry-s 0.5 > $OUT/nmfd_ws${m}_$i.json 2>> $OUT/nmfd.err
+    TORCHNMF_AMD_NMFD_WINSTAGE=$m timeout 300 python bench.py --full --workload nmfd --cpu-iters 0 --steps 50 --telemetry-s 0.5 > $OUT/nmfd_ws${m}_$i.json 2>> $OUT/nmfd.err
     python - <<PY
 import json
 try:
@@ -18,4 +18,4 @@ done
 tail -3 $OUT/nmfd.err
 NMFMU_LIB=$PWD/pytorch-nmf_amd/torchnmf_amd/libnmfmu_dbg.so timeout 300 python tools/mall_probe.py f16 > $OUT/mall_nt.json 2> $OUT/mall_nt.err; echo "mall nt rc=$?"; cat $OUT/mall_nt.err | grep -v amdgpu.ids | tail -6
 NMFMU_LIB=$PWD/pytorch-nmf_amd/torchnmf_amd/libnmfmu_dbgx.so timeout 300 python tools/mall_probe.py f16 > $OUT/mall_default.json 2> $OUT/mall_default.err; echo "mall default rc=$?"; cat $OUT/mall_default.err | grep -v amdgpu.ids | tail -6
-timeout 900 python bench.py --cpu-iters 3 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; tail -3 $OUT/bench.err; python tools/bench_brief.py $OUT/bench.json 2>&1 | tail -40
+timeout 900 python bench.py --full --cpu-iters 3 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; tail -3 $OUT/bench.err; python tools/bench_brief.py $OUT/bench.json 2>&1 | tail -40

@@ -5,7 +5,7 @@ TAG=${1:-r5c}; OUT=gpurun_out/$TAG; mkdir -p $OUT
 LIBD=$PWD/pytorch-nmf_amd/torchnmf_amd
 for v in "" _abl_NOMFMA _abl_NODMA _abl_NOFRAG _abl_NOBAR; do
   for m in 1 0; do
-    NMFMU_LIB=$LIBD/libnmfmu$v.so TORCHNMF_AMD_NMFD_WINSTAGE=$m timeout 200 python bench.py --workload nmfd --cpu-iters 0 --steps 30 --repeats 3 --telemetry-s 0.3 --no-parity-mode > $OUT/nmfd${v}_ws$m.json 2>> $OUT/err.log
+    NMFMU_LIB=$LIBD/libnmfmu$v.so TORCHNMF_AMD_NMFD_WINSTAGE=$m timeout 200 python bench.py --full --workload nmfd --cpu-iters 0 --steps 30 --repeats 3 --telemetry-s 0.3 --no-parity-mode > $OUT/nmfd${v}_ws$m.json 2>> $OUT/err.log
     python - <<PY
 import json
 try:

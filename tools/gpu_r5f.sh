@@ -4,7 +4,7 @@ TAG=${1:-r5f}; OUT=gpurun_out/$TAG; mkdir -p $OUT
 timeout 900 python -m pytest tests/test_gpu_parity.py -q -m gpu -k "launch_diet or nmf2d or nmf3d or shifted or several_shift or window_operand or convnd or siplca" > $OUT/pytest.log 2>&1; echo "pytest rc=$?"; tail -8 $OUT/pytest.log | cut -c1-250
 for i in 1 2; do
   for m in 1 0; do
-    TORCHNMF_AMD_NMFD_ROWS_FUSED=$m timeout 200 python bench.py --workload nmf2d --precision auto --cpu-iters 0 --steps 50 --repeats 3 --telemetry-s 0 > $OUT/nmf2d_fused${m}_$i.json 2>> $OUT/err.log
+    TORCHNMF_AMD_NMFD_ROWS_FUSED=$m timeout 200 python bench.py --full --workload nmf2d --precision auto --cpu-iters 0 --steps 50 --repeats 3 --telemetry-s 0 > $OUT/nmf2d_fused${m}_$i.json 2>> $OUT/err.log
     python - <<PY
 import json
 try:

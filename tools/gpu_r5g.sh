@@ -6,7 +6,7 @@ LIBD=$PWD/pytorch-nmf_amd/torchnmf_amd
 for v in "" _abl_noelem; do
   for args in "--beta 0.5" "--beta 0" "--beta 2" "--config cfg5 --steps 10"; do
     tag=$(echo $args | tr -d ' -' | tr '.' 'p')
-    NMFMU_LIB=$LIBD/libnmfmu$v.so timeout 300 python bench.py $args --no-sweep --cpu-iters 0 --no-parity-mode --repeats 3 > $OUT/b${v}_$tag.json 2>> $OUT/err.log
+    NMFMU_LIB=$LIBD/libnmfmu$v.so timeout 300 python bench.py --full $args --no-sweep --cpu-iters 0 --no-parity-mode --repeats 3 > $OUT/b${v}_$tag.json 2>> $OUT/err.log
     python - <<PY
 import json
 try:

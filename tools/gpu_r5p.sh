@@ -8,7 +8,7 @@ cd /tmp
 COMMON="--steps 8 --warmup 3 --cpu-iters 0 --repeats 1 --max-repeats 1 --preroll-s 0.1 --telemetry-s 0"
 scan() {  # name, bench args
   local name=$1; shift
-  timeout 300 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_BUSY_CYCLES SQ_WAVE_CYCLES --output-format csv -d $OUT/pmc_$name/pmc_lds -o pmc -- python $ROOT/bench.py $COMMON "$@" > /dev/null 2> $OUT/pmc_$name.err
+  timeout 300 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_BUSY_CYCLES SQ_WAVE_CYCLES --output-format csv -d $OUT/pmc_$name/pmc_lds -o pmc -- python $ROOT/bench.py --full $COMMON "$@" > /dev/null 2> $OUT/pmc_$name.err
   echo "scan $name rc=$?"
   python $ROOT/tools/pmc_summary.py $OUT/pmc_$name > $OUT/${name}_lds_pmc_summary.txt 2>&1
 }

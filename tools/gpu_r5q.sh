@@ -7,7 +7,7 @@ VARS=${VARS:-"- _xbnogemm _xbnox _xbns5 _xbpol"}
 for v in $VARS; do
   [ "$v" = "-" ] && v=""
   [ -f $LIBD/libnmfmu$v.so ] || { echo "no lib $v"; continue; }
-  NMFMU_LIB=$LIBD/libnmfmu$v.so timeout 300 python bench.py $ARGS --beta 2 --gram --no-sweep --cpu-iters 0 --no-parity-mode --repeats 3 > $OUT/b${v}.json 2>> $OUT/err.log
+  NMFMU_LIB=$LIBD/libnmfmu$v.so timeout 300 python bench.py --full $ARGS --beta 2 --gram --no-sweep --cpu-iters 0 --no-parity-mode --repeats 3 > $OUT/b${v}.json 2>> $OUT/err.log
   python - <<PY
 import json
 try:

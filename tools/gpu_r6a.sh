@@ -9,7 +9,7 @@ tools/ubench/dma_off_probe > $OUT/dma_off_probe.txt 2>&1; cat $OUT/dma_off_probe
 for i in 1 2; do
   for v in "" _dbg _dup1 _dup2 _dup4 _dup8 _dup16 _dup32; do
     [ -f $LIBD/libnmfmu$v.so ] || { echo "missing $v"; continue; }
-    NMFMU_LIB=$LIBD/libnmfmu$v.so timeout 300 python bench.py --steps 40 --warmup 10 --cpu-iters 0 --no-sweep --no-parity-mode --repeats 3 > $OUT/b${v}_$i.json 2>> $OUT/err.log
+    NMFMU_LIB=$LIBD/libnmfmu$v.so timeout 300 python bench.py --full --steps 40 --warmup 10 --cpu-iters 0 --no-sweep --no-parity-mode --repeats 3 > $OUT/b${v}_$i.json 2>> $OUT/err.log
     python - <<PY
 import json
 try:
@@ -25,7 +25,7 @@ done
 # baselines of the kernels this round works on (shipped library): configs[4]'s shard, beta sweep legs
 for args in "--config cfg5 --steps 10" "--beta 0.5" "--beta 0"; do
   tag=$(echo $args | tr -d ' -' | tr '.' 'p')
-  timeout 300 python bench.py $args --no-sweep --cpu-iters 0 --no-parity-mode --repeats 3 > $OUT/base_$tag.json 2>> $OUT/err.log
+  timeout 300 python bench.py --full $args --no-sweep --cpu-iters 0 --no-parity-mode --repeats 3 > $OUT/base_$tag.json 2>> $OUT/err.log
   python - <<PY
 import json
 try:

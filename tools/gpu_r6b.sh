@@ -12,7 +12,7 @@ done
 for i in 1 2; do
   for cfg in "_nosp:" "_nosp:4" ":" ":8"; do
     v=${cfg%%:*}; ns=${cfg##*:}
-    TORCHNMF_AMD_NSPLIT=$ns NMFMU_LIB=$LIBD/libnmfmu$v.so timeout 300 python bench.py --config cfg5 --steps 10 --no-sweep --cpu-iters 0 --no-parity-mode --repeats 3 > $OUT/cfg5${v}_ns${ns}_$i.json 2>> $OUT/err.log
+    TORCHNMF_AMD_NSPLIT=$ns NMFMU_LIB=$LIBD/libnmfmu$v.so timeout 300 python bench.py --full --config cfg5 --steps 10 --no-sweep --cpu-iters 0 --no-parity-mode --repeats 3 > $OUT/cfg5${v}_ns${ns}_$i.json 2>> $OUT/err.log
     python - <<PY
 import json
 try:
@@ -25,7 +25,7 @@ done
 for i in 1 2; do
   for v in _dbg _dup4 _dup32; do
     [ -f $LIBD/libnmfmu$v.so ] || { echo "missing $v"; continue; }
-    NMFMU_LIB=$LIBD/libnmfmu$v.so timeout 300 python bench.py --steps 40 --warmup 10 --cpu-iters 0 --no-sweep --no-parity-mode --repeats 3 > $OUT/b${v}_$i.json 2>> $OUT/err.log
+    NMFMU_LIB=$LIBD/libnmfmu$v.so timeout 300 python bench.py --full --steps 40 --warmup 10 --cpu-iters 0 --no-sweep --no-parity-mode --repeats 3 > $OUT/b${v}_$i.json 2>> $OUT/err.log
     python - <<PY
 import json
 try:

@@ -10,7 +10,7 @@ done
 for i in 1 2; do
   for cfg in "_nosp:" ":" ":8" ${EXTRA_CFGS}; do
     v=${cfg%%:*}; ns=${cfg##*:}
-    TORCHNMF_AMD_NSPLIT=$ns NMFMU_LIB=$LIBD/libnmfmu$v.so timeout 300 python bench.py --config cfg5 --steps 10 --no-sweep --cpu-iters 0 --no-parity-mode --repeats 3 > $OUT/cfg5${v}_ns${ns}_$i.json 2>> $OUT/err.log
+    TORCHNMF_AMD_NSPLIT=$ns NMFMU_LIB=$LIBD/libnmfmu$v.so timeout 300 python bench.py --full --config cfg5 --steps 10 --no-sweep --cpu-iters 0 --no-parity-mode --repeats 3 > $OUT/cfg5${v}_ns${ns}_$i.json 2>> $OUT/err.log
     python - <<PY
 import json
 try:

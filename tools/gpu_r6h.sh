@@ -1,7 +1,7 @@
 #!/bin/bash
 TAG=${1:-r6h}; OUT=gpurun_out/$TAG; mkdir -p $OUT
 timeout 1200 python -m pytest tests/test_gpu_parity.py -q -m gpu -k "betamu" 2>&1 | tail -15 | tee $OUT/pytest_betamu.txt
-timeout 300 python bench.py --steps 20 --cpu-iters 0 --no-parity-mode --no-sweep > $OUT/bench_cfg1.json 2>> $OUT/err.log
+timeout 300 python bench.py --full --steps 20 --cpu-iters 0 --no-parity-mode --no-sweep > $OUT/bench_cfg1.json 2>> $OUT/err.log
 python - <<PY
 import json
 d=json.load(open("$OUT/bench_cfg1.json")); r=d["roofline"]

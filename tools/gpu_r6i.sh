@@ -6,7 +6,7 @@ timeout 1500 python -m pytest tests/test_gpu_parity.py -q -m gpu -k "rank128_two
 for i in 1 2; do
   for v in _nosp2 ""; do
     for b in 0.5 0 1.5 0.3; do
-      NMFMU_LIB=$LIBD/libnmfmu$v.so timeout 300 python bench.py --beta $b --steps 20 --no-sweep --cpu-iters 0 --no-parity-mode --repeats 3 > $OUT/b${v}_$b_$i.json 2>> $OUT/err.log
+      NMFMU_LIB=$LIBD/libnmfmu$v.so timeout 300 python bench.py --full --beta $b --steps 20 --no-sweep --cpu-iters 0 --no-parity-mode --repeats 3 > $OUT/b${v}_$b_$i.json 2>> $OUT/err.log
       python - <<PY
 import json
 try:

@@ -10,6 +10,6 @@ for b in 0 0.5 0.3; do
   done
 done
 for b in 0 0.5; do
-timeout 300 python bench.py --beta $b --steps 20 --no-sweep --cpu-iters 0 --no-parity-mode --repeats 3 2>/dev/null | python -c "import json,sys; d=json.load(sys.stdin); r=d['roofline']; print('beta=$b: it/s', d['iters_per_s'], 'kernel_ms', r['avg_launch_ms'], 'frac', r['frac'])"
+timeout 300 python bench.py --full --beta $b --steps 20 --no-sweep --cpu-iters 0 --no-parity-mode --repeats 3 2>/dev/null | python -c "import json,sys; d=json.load(sys.stdin); r=d['roofline']; print('beta=$b: it/s', d['iters_per_s'], 'kernel_ms', r['avg_launch_ms'], 'frac', r['frac'])"
 done
 timeout 900 python -m pytest tests/test_gpu_parity.py -q -m gpu -k "rank128_two_accumulator or cfg2_full_size" 2>&1 | tail -3

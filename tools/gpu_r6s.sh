@@ -1,7 +1,7 @@
 #!/bin/bash
 # round 6: the default bench line on the final build (host-side changes after the evidence call), with its wall time
 OUT=gpurun_out/r6s; mkdir -p $OUT
-T0=$(date +%s); timeout 1200 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$? wall $(( $(date +%s) - T0 )) s"; python tools/bench_brief.py $OUT/bench.json 2>&1 | head -8
+T0=$(date +%s); timeout 1200 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$? wall $(( $(date +%s) - T0 )) s"; python tools/bench_brief.py $OUT/bench.json 2>&1 | head -8
 python - <<'PY'
 import json
 d=json.load(open('gpurun_out/r6s/bench.json'))

@@ -7,7 +7,7 @@ timeout 1800 python -m pytest tests/test_gpu_parity.py tests/test_gpu_fuzz.py -q
 for rep in 1 2 3; do
 for v in _epi0 ""; do
 for b in 0.5 0 1.5; do
-NMFMU_LIB=$LIBD/libnmfmu$v.so timeout 300 python bench.py --beta $b --steps 20 --no-sweep --cpu-iters 0 --no-parity-mode --repeats 3 2>/dev/null | python -c "
+NMFMU_LIB=$LIBD/libnmfmu$v.so timeout 300 python bench.py --full --beta $b --steps 20 --no-sweep --cpu-iters 0 --no-parity-mode --repeats 3 2>/dev/null | python -c "
 import json,sys; d=json.load(sys.stdin); r=d['roofline']
 print('lib$v beta=$b: it/s', d['iters_per_s'], 'kernel_ms', r['avg_launch_ms'], 'w/h', r.get('avg_launch_ms_w_step'), r.get('avg_launch_ms_h_step'), 'frac', r['frac'])" | tee -a $OUT/sp2_staged.txt
 done; done; done

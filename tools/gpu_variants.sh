@@ -5,7 +5,7 @@ OUT=gpurun_out/$TAG; mkdir -p $OUT
 for i in 1 2; do
   for v in "$@"; do
     lib=$PWD/pytorch-nmf_amd/torchnmf_amd/libnmfmu$v.so
-    NMFMU_LIB=$lib timeout 300 python bench.py --steps 40 --warmup 10 --cpu-iters 0 ${BENCH_ARGS} > $OUT/v_${v}_$i.json 2>> $OUT/v.err
+    NMFMU_LIB=$lib timeout 300 python bench.py --full --steps 40 --warmup 10 --cpu-iters 0 ${BENCH_ARGS} > $OUT/v_${v}_$i.json 2>> $OUT/v.err
     python - <<PY
 import json
 try:

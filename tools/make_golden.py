@@ -23,6 +23,8 @@ Sets:
   g10_plca       plca.PLCA.fit (EM, plca.py:244-304): plain / Dirichlet priors / frozen Z / frozen W
   g12_betamu_chain  trainer.BetaMu.step on a three-layer nn.Sequential of NMF layers (tests/test_trainer.py:10-32)
   g7_betamu      trainer.BetaMu.step on one NMF layer: every beta x penalties, factors after 1 and 5 steps, p.grad
+  g7_hosts       g7's factors after 5 steps ('both' cases) as the reference computes them on the running host, appended to
+                 g7_betamu_hosts.npz when no recorded run has the same bits (sgemm kernels differ between CPUs)
   g14_betamu_conv  trainer.BetaMu.step on ONE convolutive layer (NMFD / NMF2D / NMF3D): beta in {0.5, 1, 2} x penalties,
                  factors after 1 and 3 steps, p.grad of the first step
 """
@@ -222,6 +224,40 @@ def g7():
     out['cases'] = np.array(cases)
     out['param_order'] = np.array([n for n, _ in torchnmf.nmf.NMF((4, 3), rank=2).named_parameters()])
     np.savez_compressed(os.path.join(OUT, 'g7_betamu.npz'), **out)
+
+
+def g7_hosts():
+    """The last bits of g7's 'both' factors after 5 steps follow the host's sgemm kernels, the reference's as much as
+    anyone's.  Runs the reference on g7's stored inputs on THIS host and appends its factors to g7_betamu_hosts.npz when
+    they differ from every run recorded so far (g7_betamu.npz and this file): the bit-identity test of the CPU port
+    accepts any recorded run of the reference."""
+    from torchnmf.trainer import BetaMu
+    g = np.load(os.path.join(OUT, 'g7_betamu.npz'))
+    path = os.path.join(OUT, 'g7_betamu_hosts.npz')
+    old = dict(np.load(path)) if os.path.exists(path) else {'hosts': np.array([], dtype=str)}
+    V, W0, H0 = (torch.from_numpy(g[k]) for k in ('V', 'W0', 'H0'))
+    run = {}
+    for beta in [-1, 0, 0.5, 1, 1.5, 2, 3]:
+        for name, (l1, l2, ortho) in {'plain': (0, 0, 0), 'pen': (1e-3, 1e-3, 1e-2)}.items():
+            m = torchnmf.nmf.NMF(W=W0.clone(), H=H0.clone())
+            trainer = BetaMu(list(m.parameters()), beta, l1, l2, ortho)
+
+            def closure():
+                trainer.zero_grad()
+                return V, m()
+            for _ in range(5):
+                trainer.step(closure)
+            run[f'b{beta}_{name}_both_W5'] = m.W.detach().numpy().copy()
+            run[f'b{beta}_{name}_both_H5'] = m.H.detach().numpy().copy()
+    recorded = [{k: g[k] for k in run}] + [{k: old[f'h{i}_{k}'] for k in run} for i in range(len(old['hosts']))]
+    if any(all(np.array_equal(r[k], v) for k, v in run.items()) for r in recorded):
+        print('g7_hosts: this host reproduces a recorded run; nothing to add')
+        return
+    i = len(old['hosts'])
+    old.update({f'h{i}_{k}': v for k, v in run.items()})
+    old['hosts'] = np.array(list(old['hosts']) + [f'torch {torch.__version__}, CPU capability '
+                                                  f'{torch.backends.cpu.get_cpu_capability()}, 1 thread'])
+    np.savez_compressed(path, **old)
 
 
 def g8():
@@ -458,7 +494,8 @@ if __name__ == '__main__':
     torch.set_num_threads(1)  # reproducible summation order
     assert torchnmf.__version__ == '0.3.5', torchnmf.__version__
     # `python tools/make_golden.py g13` regenerates only the named sets (round 5 added g13 without touching the others)
-    todo = [fn for fn in (g1, g2, g3, g4, g5, g6, g7, g8, g9, g10, g11, g12, g13, g14) if len(sys.argv) < 2 or fn.__name__ in sys.argv[1:]]
+    todo = [fn for fn in (g1, g2, g3, g4, g5, g6, g7, g8, g9, g10, g11, g12, g13, g14, g7_hosts)
+            if len(sys.argv) < 2 or fn.__name__ in sys.argv[1:]]
     for fn in todo:
         fn()
         print('wrote', fn.__name__)
@@ -466,4 +503,4 @@ if __name__ == '__main__':
         if len(sys.argv) > 1:
             f.write(f'{" ".join(sys.argv[1:])}: ')
         f.write(f'generated by tools/make_golden.py from torchnmf {torchnmf.__version__} '
-                f'(reference mounted at {REF}), torch {torch.__version__}, CPU fp32, 1 thread\n')
+                f'(the reference, imported), torch {torch.__version__}, CPU fp32, 1 thread\n')
