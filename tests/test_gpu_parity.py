@@ -19,6 +19,7 @@ import pytest
 import torch
 
 from conftest import load_golden, record, rel_err
+from mu_emulation import split_tiles
 
 _ORACLE_CACHE = {}   # (test, shape, beta) -> oracle factors, shared by the parametrizations that differ only in the operand mode
 
@@ -2431,7 +2432,8 @@ def test_cfg5_shard_slice_rank256(dev, prec, tol):
                                               (600, 1000, 2, (0.1, 0.5)),        # 8 + 8 tiles, regularised (general epilogue)
                                               (400, 1300, 3, (0.0, 0.0)),        # 24 tiles in splits of 8
                                               (260, 2100, 5, (0.0, 0.0)),        # 36 tiles in splits of 8: the last split holds 4
-                                              (1100, 300, 8, (0.3, 0.0))])       # more splits than groups: empty workgroups
+                                              (1100, 300, 8, (0.3, 0.0)),        # nsplit clamps to k_pad // 256: splits of 4, none empty
+                                              (300, 1200, 4, (0.0, 0.0))])       # H half-step: 20 tiles as [8, 8, 4, 0], an empty split
 def test_rank256_software_pipelined_kernel(dev, monkeypatch, N, C, nsplit, regs):
     """nmfmu::sp_kernel (round 6: padded rank 256, beta = 1, fp16 -- the kernel of configs[4]'s shard) over its control
     flow: one / several four-tile groups, the last group's shorter final iteration, contraction splits that leave short and
@@ -2453,6 +2455,8 @@ def test_rank256_software_pipelined_kernel(dev, monkeypatch, N, C, nsplit, regs)
     W, H = W0.clone().to(dev), H0.clone().to(dev)
     eng = DenseMU(V.to(dev), W, H, 1.0, alpha * l1r, alpha * (1 - l1r), precision='f16')
     assert eng.r_pad == 256 and eng.be.kernel_family(256, _capi.PREC_F16, 1.0) == _capi.KERNEL_SP
+    if (N, C, nsplit) == (300, 1200, 4):     # (host mirror of the split: the H half-step's last workgroups get no tile)
+        assert split_tiles(eng.step_h.panel.rows_pad, eng.step_h.nsplit, 'sp') == [8, 8, 4, 0]
     Wr, Hr = W0, H0
     for _ in range(2):
         eng.w_step()
@@ -2517,7 +2521,8 @@ def test_cfg5_full_shard_two_iterations(dev):
                                               (130, 500, None, (0.0, 0.0)),      # 8 tiles: one pass of the loop + the last group
                                               (600, 1000, 1, (0.1, 0.5)),        # 16 tiles unsplit: fused apply, regularised
                                               (260, 2100, 5, (0.0, 0.0)),        # 36 tiles in splits of 8: the last split holds 4
-                                              (1100, 300, 8, (0.0, 0.0))])       # more splits than groups: empty workgroups
+                                              (1100, 300, 8, (0.0, 0.0)),        # nsplit clamps to k_pad // 256: splits of 4, none empty
+                                              (300, 1200, 4, (0.0, 0.0))])       # H half-step: 20 tiles as [8, 8, 4, 0], an empty split
 def test_rank128_two_accumulator_software_pipelined_kernel(dev, monkeypatch, beta, N, C, nsplit, regs):
     """nmfmu::sp2_kernel (round 6: padded rank 128, beta not in {1, 2}, fp16 -- the kernel of configs[2]'s beta < 1 legs) over
     its control flow -- one / several four-tile groups, the last group's shorter final iteration, contraction splits with
@@ -2540,6 +2545,8 @@ def test_rank128_two_accumulator_software_pipelined_kernel(dev, monkeypatch, bet
     W, H = W0.clone().to(dev), H0.clone().to(dev)
     eng = DenseMU(V.to(dev), W, H, beta, alpha * l1r, alpha * (1 - l1r), precision='f16')
     assert eng.r_pad == 128 and eng.be.kernel_family(128, _capi.PREC_F16, float(beta)) == _capi.KERNEL_SP
+    if (N, C, nsplit) == (300, 1200, 4):     # (host mirror of the split: the H half-step's last workgroups get no tile)
+        assert split_tiles(eng.step_h.panel.rows_pad, eng.step_h.nsplit, 'sp') == [8, 8, 4, 0]
     Wr, Hr = W0, H0
     for _ in range(2):
         eng.w_step()
@@ -2610,6 +2617,7 @@ def test_f16r_target_packing_is_the_top_24_bits(dev):
     and compare with the fp32 rounded to nearest-even at bit 8: bit-exact, relative error <= 2^-16 everywhere in fp32's range
     (subnormals: absolute 2^-142), zero / one / huge / tiny values, a value that would round up to infinity truncated."""
     from torchnmf_amd import _capi
+    from mu_emulation import round24_bits
     lib = _capi.load()
     N, C = 256, 256
     g = torch.Generator().manual_seed(19)
@@ -2633,8 +2641,8 @@ def test_f16r_target_packing_is_the_top_24_bits(dev):
     roff = ((base + 4 + i // 16) * 64 + lane) * 16 + (i % 16)
     got = (raw[hoff + 1] << 24) | (raw[hoff] << 16) | (raw[roff] << 8)
     bits = V.numpy().view(np.uint32).astype(np.uint64)
-    want = (bits + 0x7f + ((bits >> 8) & 1)) & 0xffffff00
-    want[0, 8] = 0x7f7fff00
+    want = round24_bits(bits)
+    assert want[0, 8] == 0x7f7fff00
     assert np.array_equal(got.astype(np.uint64), want)
     dec = got.astype(np.uint32).view(np.float32).astype(np.float64)
     ref = V.numpy().astype(np.float64)
