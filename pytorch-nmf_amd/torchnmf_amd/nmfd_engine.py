@@ -157,6 +157,9 @@ class ConvMU(AsyncLossMixin):
                     precision = 'f16'
         if precision not in _capi.PRECISIONS:
             raise ValueError(f"precision must be one of {sorted(_capi.PRECISIONS)} or 'auto', got {precision!r}")
+        if precision in ('f16r', 'f16x'):
+            raise ValueError(f"precision {precision!r} belongs to the dense rank <= 256 kernels; the convolutive engine (NMFD, "
+                             "NMF2D, NMF3D, ranks above 256) is built for 'bf16', 'bf16x3' and 'f16'")
         if precision == 'f16' and not f16_ok:
             raise ValueError("precision 'f16' is built for the convolutive models with beta == 1 and taps / frames (of the "
                              "last shift axis) that are multiples of 8 (implicit Toeplitz operands), on shapes whose H "
@@ -536,8 +539,9 @@ class ConvMU(AsyncLossMixin):
             self._gemm(self.gp, self.hut, _capi.EPI_F32, out=self.den_w, k_split=self.w_ksplit, m_rows=self.c_rows)
         self._pack_w(update=True)
 
-    def h_step(self):
-        """nmf.py:380-391 for the conv1d model (uses the freshly updated W)."""
+    def recon_ratio_h(self):
+        """Reconstruction + ratio planes of the H half-step (the transposed problem Hu Wm^T against V^T), split like
+        ``recon_ratio_w``."""
         if self.ragged:
             self._gemm(self.hu, self.wm, _capi.EPI_RATIO, x=self.x_h, gn=self.gnt, gp=self.gpt, n_rows=self.c_main,
                        ragged=self.ragged_in_grid, tag='recon_h')
@@ -546,6 +550,10 @@ class ConvMU(AsyncLossMixin):
         else:
             self._gemm(self.hu, self.wm, _capi.EPI_RATIO, x=self.x_h, gn=self.gnt, gp=self.gpt, n_rows=self.c_rows,
                        tag='recon_h')
+
+    def h_step(self):
+        """nmf.py:380-391 for the conv1d model (uses the freshly updated W)."""
+        self.recon_ratio_h()
         if self.h_rows:
             self._gemm_win(self.gnt, self.hnum, tag='num_h')
             if not self.kl:

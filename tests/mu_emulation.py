@@ -177,14 +177,16 @@ AMBIGUITY = 2e-6
 
 
 def half_step(X, A, B, beta: float, precision: str, *, M=None, K=None, cs_owner=None, cs_panel=None, rounding=True,
-              A_img=None, B_img=None, ratio_round=None):
+              A_img=None, B_img=None, ratio_round=None, x_stored=None):
     """Numerator and denominator of one half-step, float64, [rows of A] x rank.
 
     X: [m, k] fp32 target rows (V or V^T); A: [m, R] owner rows; B: [k, R] panel.  ``A_img`` / ``B_img`` = (hi, lo or None)
     image planes to use instead of rounding A / B (the tests pass the images read back from the GPU).  M, K: the full
     owner / contraction lengths (ki), default the shapes given.  cs_owner / cs_panel: the column sums the kernel reads
     (ki).  rounding=False: every operand exact (the plain float64 algorithm of mu_oracle).  ``ratio_round(G, split)``:
-    replaces the Gn / Gp rounding (seeded-fault tests).
+    replaces the Gn / Gp rounding (seeded-fault tests).  ``x_stored``:
+    the target as the kernel holds it, used instead of ``stored_target(X, precision)`` (the convolutive engine keeps fp32
+    targets in every precision: tests/conv_emulation.py).
 
     Returns a dict: num, den (None at beta == 1), ki, and num_amb / den_amb -- per element, the largest difference that
     the ambiguous terms (AMBIGUITY) can make."""
@@ -195,7 +197,7 @@ def half_step(X, A, B, beta: float, precision: str, *, M=None, K=None, cs_owner=
     if rounding:
         Ah, Al = A_img if A_img is not None else factor_image(A, precision)
         Bh, Bl = B_img if B_img is not None else factor_image(B, precision)
-        x = stored_target(X, precision)
+        x = stored_target(X, precision) if x_stored is None else np.asarray(x_stored, dtype=np.float64)
     else:
         Ah, Al, Bh, Bl, x = (np.asarray(A, np.float64), None, np.asarray(B, np.float64), None, X)
     S = _gemm([Ah] if Al is None else [Ah, Al], Bh.T, None if Bl is None else Bl.T)

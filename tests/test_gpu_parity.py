@@ -1738,6 +1738,12 @@ def test_unsupported_combinations_raise(dev):
     assert m.fit(V.to(dev), max_iter=3) == 3                       # which is also what 'auto' means above rank 128
     assert m.fit(V.to(dev), max_iter=3, precision='bf16') == 3     # the fast fused kernel on request
     assert NMF(V.shape, 300).to(dev).fit(V.to(dev), max_iter=3) == 3   # rank > 256: GEMM engine (WideRankMU)
+    # the dense-only operand modes are refused by the convolutive engine up front, not by a bare ERR_ARG at the first pack
+    from torchnmf_amd.nmfd_engine import ConvMU
+    Vc, Wc, Hc = torch.rand(1, 20, 40), torch.rand(20, 3, 8), torch.rand(1, 3, 33)
+    for prec in ('f16r', 'f16x'):
+        with pytest.raises(ValueError, match='convolutive engine'):
+            ConvMU(Vc.to(dev), Wc.to(dev), Hc.to(dev), 1.0, precision=prec)
 
 
 # ----------------------------------------------------------------------------------------------------------
