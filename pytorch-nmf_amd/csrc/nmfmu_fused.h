@@ -59,6 +59,7 @@
 
 #include <type_traits>
 
+#include "nmfmu_launch.h"
 #include "nmfmu_layout.h"
 
 #ifndef NMFMU_FUSED_G1_ASM
@@ -1173,28 +1174,10 @@ int launch_fused_r64(int beta_kind, int prec, int mode, const FusedArgs& a, int 
 int launch_fused_r128(int beta_kind, int prec, int mode, const FusedArgs& a, int grid, hipStream_t s);
 int launch_fused_r256(int beta_kind, int prec, int mode, const FusedArgs& a, int grid, hipStream_t s);
 
-// Per-device "attribute set" memo (one host thread may drive several devices)
-inline bool* attr_flag(bool (&flags)[64]) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  return &flags[dev];
-}
-
 template <int R_PAD, int BETA, int PREC, int MODE>
 int launch_one(const FusedArgs& a, int grid, hipStream_t s) {
   using C = FusedCfg<R_PAD, BETA, PREC, MODE>;
-  static_assert(C::LDS_BYTES <= 160 * 1024, "LDS budget");
-  auto kern = fused_kernel<R_PAD, BETA, PREC, MODE>;
-  static bool done[64] = {};   // the dynamic-LDS attribute is per device: a single-process multi-device host sets it on each
-  bool* flag = attr_flag(done);
-  if (!*flag) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       C::LDS_BYTES);
-    if (e != hipSuccess) return (int)e;
-    *flag = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(C::THREADS), C::LDS_BYTES, s, a);
-  return (int)hipGetLastError();
+  return launch_with_dynamic_lds<fused_kernel<R_PAD, BETA, PREC, MODE>, C::THREADS, C::LDS_BYTES>(dim3(grid), s, a);
 }
 
 // Instantiation table.  beta == 1 with one operand plane at padded rank <= 128 belongs to the ping-pong kernel

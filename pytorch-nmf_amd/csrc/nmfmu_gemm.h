@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "nmfmu_fused.h"
+#include "nmfmu_launch.h"
 
 namespace nmfmu {
 
@@ -723,24 +724,14 @@ int launch_gemm_one(const GemmArgs& a, hipStream_t s) {
   constexpr int kFoldBytes = (SH::THREADS / 256) * 128 * kFoldLd * 4;
   constexpr bool kRag = EPI == kEpiRatio && (OPS == kOpsBHu || OPS == kOpsAHu) && SH::THREADS == 256;
   constexpr int kLds = (EPI == kEpiFold && C::LDS_BYTES < kFoldBytes) ? kFoldBytes : C::LDS_BYTES + (kRag ? C::RAG_BYTES : 0);
-  static_assert(kLds <= 160 * 1024, "LDS budget");
   if (a.m_pad % C::BM || a.n_pad % C::BN) return -3;
-  auto kern = nt_gemm_kernel<X3, EPI, BETA, OPS, SH, OPT, ND, WS>;
-  static bool done[64] = {};   // per device (nmfmu_fused.h: attr_flag)
-  bool* flag = attr_flag(done);
-  if (!*flag) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       kLds);
-    if (e != hipSuccess) return (int)e;
-    *flag = true;
-  }
   if (a.k_split > 1 && EPI != kEpiF32 && !(EPI == kEpiFold && a.tail_rows > 0)) return -3;
   if (a.rag_C > a.rag_c0) {   // eight workgroups share out a tile's 128 frames: the other dimension needs >= 8 tiles
     if (!kRag || a.rag_C - a.rag_c0 > 16 || (OPS == kOpsBHu ? a.m_pad : a.n_pad) < 8 * 128) return -3;
   }
   const int grid_y = a.m_pad / C::BM + (EPI == kEpiFold ? a.tail_rows * (a.k_split - 1) : 0);
-  hipLaunchKernelGGL(kern, dim3(a.n_pad / C::BN, grid_y, EPI == kEpiFold ? 1 : a.k_split), dim3(SH::THREADS), kLds, s, a);
-  return (int)hipGetLastError();
+  return launch_with_dynamic_lds<nt_gemm_kernel<X3, EPI, BETA, OPS, SH, OPT, ND, WS>, SH::THREADS, kLds>(
+      dim3(a.n_pad / C::BN, grid_y, EPI == kEpiFold ? 1 : a.k_split), s, a);
 }
 
 // f16 != 0: fp16 operand planes / window tables and fp16 ratio planes (single plane; the beta == 1 NMFD path)

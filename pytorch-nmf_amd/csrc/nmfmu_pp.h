@@ -51,9 +51,6 @@
 #pragma once
 #include "nmfmu_fused.h"
 
-#ifndef NMFMU_PP_EPI_PLAIN
-#define NMFMU_PP_EPI_PLAIN 1  // fused apply: branch-free form for the unregularised full-tile case
-#endif
 // Joule budget by result-preserving DUPLICATION (round 6; tools/gpu_r6a.sh, profiles/r06_joule_budget.md):
 // -DNMFMU_PP_DUP=<bits> executes one component of the tile loop TWICE with identical results (every earlier energy
 // experiment was a deletion, which corrupts the factors -- and the clock follows the data).  1: every panel ds_read_b128;
@@ -797,7 +794,7 @@ __global__ void __launch_bounds__(512, 2) pp_kernel(const FusedArgs a) {
       // valid -- without the per-element branches, bounds tests and IEEE divisions of the general form below: the
       // denominators are the same for every row, so their reciprocals are taken once (the multiplier then differs from
       // the correctly rounded quotient by at most one ulp).
-      const bool plain = NMFMU_PP_EPI_PLAIN && a.l1 <= 0.f && a.l2 <= 0.f && a.gamma == 1.f && a.rank == R_PAD &&
+      const bool plain = a.l1 <= 0.f && a.l2 <= 0.f && a.gamma == 1.f && a.rank == R_PAD &&
                          mb * C::BM + C::BM <= a.M;
       if (plain) {
         float rden8[8];
@@ -936,18 +933,7 @@ __global__ void __launch_bounds__(512, 2) pp_kernel(const FusedArgs a) {
 template <int R_PAD, int OPT, int MODE, bool XR = false, bool LACC = false>
 int launch_pp_one(const FusedArgs& a, int grid, hipStream_t s) {
   using C = PPCfg<R_PAD, OPT, MODE, XR, LACC>;
-  static_assert(C::LDS_BYTES <= 160 * 1024, "LDS budget");
-  auto kern = pp_kernel<R_PAD, OPT, MODE, XR, LACC>;
-  static bool done[64] = {};
-  bool* flag = attr_flag(done);
-  if (!*flag) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       C::LDS_BYTES);
-    if (e != hipSuccess) return (int)e;
-    *flag = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(C::THREADS), C::LDS_BYTES, s, a);
-  return (int)hipGetLastError();
+  return launch_with_dynamic_lds<pp_kernel<R_PAD, OPT, MODE, XR, LACC>, C::THREADS, C::LDS_BYTES>(dim3(grid), s, a);
 }
 
 // Host-side launcher (nmfmu_inst_pp.hip).  opt = OperandType, mode = kModeMU | kModeLoss.

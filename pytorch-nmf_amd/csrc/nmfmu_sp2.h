@@ -539,18 +539,7 @@ __global__ void __launch_bounds__(256, 1) sp2_kernel(const FusedArgs a) {
 template <int R_PAD, int OPT, int BETA>
 int launch_sp2_one(const FusedArgs& a, int grid, hipStream_t s) {
   using C = SP2Cfg<R_PAD, OPT, BETA>;
-  static_assert(C::LDS_BYTES <= 160 * 1024, "LDS budget");
-  auto kern = sp2_kernel<R_PAD, OPT, BETA>;
-  static bool done[64] = {};
-  bool* flag = attr_flag(done);
-  if (!*flag) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       C::LDS_BYTES);
-    if (e != hipSuccess) return (int)e;
-    *flag = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(C::THREADS), C::LDS_BYTES, s, a);
-  return (int)hipGetLastError();
+  return launch_with_dynamic_lds<sp2_kernel<R_PAD, OPT, BETA>, C::THREADS, C::LDS_BYTES>(dim3(grid), s, a);
 }
 
 // Host-side launcher (nmfmu_inst_sp.hip).  beta_kind = BetaKind (kIS, kSqrt, kSqrt3, kGen); fp16 operands and target; padded rank 128.
