@@ -404,7 +404,7 @@ def sp_terms(idx, vals, W, H, beta):
     ii, jj = idx[0], idx[1]
     if beta == 2:
         pos = ((H @ W.t() @ W).reshape(-1) @ H.reshape(-1)) * 0.5
-        VtH = torch.zeros(W.shape[0], H.shape[1]).index_add_(0, jj, vals[:, None] * H[ii])
+        VtH = torch.zeros(W.shape[0], H.shape[1], dtype=H.dtype).index_add_(0, jj, vals[:, None] * H[ii])
         return pos, VtH.reshape(-1) @ W.reshape(-1)
     s = (W[jj] * H[ii]).sum(1)
     if beta == 1:

@@ -1,13 +1,16 @@
-// Sparse-COO targets (reference: nmf.py:351-398, 602-638), beta in {1, 2}.
+// Sparse-COO targets (reference: nmf.py:351-398, 602-638), every beta > 0: beta == 1, beta == 2 and the generic branch.
 //
 // The target is stored as CSR over the OWNER axis of a half-step (rows of V for the H half-step, rows of V^T for the
 // W half-step).  One wave per owner row; the lanes span the rank, so every panel row is one coalesced read:
 //   s   = <owner[row], panel[col]>                       wave reduction (fixed order -> deterministic)
-//   g   = v / (s + eps)   (beta == 1)    |    v          (beta == 2)
+//   g   = v / (s + eps)   (beta == 1)    |    v   (beta == 2)    |    v (s + eps)^(beta - 2)   (any other beta > 0)
 //   num[row][:] += g * panel[col][:]
 // HBM / L2-gather bound by design (2 R flops per stored entry and panel element); no MFMA, no reshaping into GEMMs.
-// The denominators are the dense closed forms: column sums of the panel (beta == 1, nmf.py:122-131) or
-// owner @ (panel^T panel) (beta == 2: the gradient of the reference's pos = 1/2 <H W^T W, H>, nmf.py:616-617).
+// The denominators of beta == 1 and beta == 2 are the dense closed forms: column sums of the panel (nmf.py:122-131) or
+// owner @ (panel^T panel) (the gradient of the reference's pos = 1/2 <H W^T W, H>, nmf.py:616-617; nmfmu_gram and
+// nmfmu_rowmat below).  The generic branch's positive term runs over EVERY entry of the reconstruction (nmf.py:628-636):
+// its denominator is a dense pass of the fused kernel without a target (nmfmu_den_partial, nmfmu_capi.hip), not in this
+// file.  nmfmu_sp_loss_neg is the O(nnz) term of the tracked loss for all three.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 

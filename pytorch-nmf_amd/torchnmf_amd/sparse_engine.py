@@ -64,6 +64,7 @@ class SparseMU:
         self.csr_h = _csr(idx[0], idx[1], vals, N)       # owner = rows of V  (H half-step, loss)
         self.csr_w = _csr(idx[1], idx[0], vals, Cc)      # owner = rows of V^T (W half-step)
         self.vals = vals
+        self._no_entries = torch.zeros(4, dtype=torch.float32, device=dev)
         # beta in {1, 2}: the images are never read (bf16 keeps them small).  Generic beta: the dense denominator pass
         # reads them -- fp32-grade split-bf16 where the fused kernel has it (padded rank <= 128), else bf16.
         prec = _capi.PREC_BF16
@@ -110,14 +111,23 @@ class SparseMU:
     def target_flags(self):
         return self.bad, self.has_zero
 
-    def _half_step(self, st: StepBuf, csr):
+    def _entries(self, t: torch.Tensor) -> int:
+        """Pointer to the column indices / values of a CSR copy.  A target without a stored entry has empty tensors, whose
+        pointer is null; the kernels never read past rowptr's ranges, so any valid address serves them."""
+        return t.data_ptr() if t.numel() else self._no_entries.data_ptr()
+
+    def _numerator(self, st: StepBuf, csr):
+        """num1 rows < owner.rows (every padded rank column written): the gather kernel over the owner's CSR rows."""
         rowptr, colidx, vals = csr
         own, pan = st.owner, st.panel
-        _capi.check(self.lib.nmfmu_sp_partial(rowptr.data_ptr(), colidx.data_ptr(), vals.data_ptr(), own.rows,
+        _capi.check(self.lib.nmfmu_sp_partial(rowptr.data_ptr(), self._entries(colidx), self._entries(vals), own.rows,
                                               own.f.data_ptr(), pan.f.data_ptr(), self.rank, self.beta,
                                               st.num1.data_ptr(), self.r_pad, self._s()), 'nmfmu_sp_partial')
+
+    def _denominator(self, st: StepBuf):
+        """den1 (beta != 1; beta == 1 reads the panel's column sums as they are)."""
+        own, pan = st.owner, st.panel
         if self.kl:
-            self.be.mu_apply(st, st.num1, None, 1, pan.colsum)
             return
         if self.generic:     # dense positive term on the fused kernel (no target), contraction-split slabs summed in order
             _capi.check(self.lib.nmfmu_den_partial(C.byref(st.struct), self._s()), 'nmfmu_den_partial')
@@ -127,7 +137,17 @@ class SparseMU:
                                             self.gram.data_ptr(), self._s()), 'nmfmu_gram')
             _capi.check(self.lib.nmfmu_rowmat(own.f.data_ptr(), own.rows, self.rank, self.gram.data_ptr(),
                                               st.den1.data_ptr(), self.r_pad, self._s()), 'nmfmu_rowmat')
-        self.be.mu_apply(st, st.num1, st.den1, 1, None)
+
+    def _apply(self, st: StepBuf):
+        if self.kl:
+            self.be.mu_apply(st, st.num1, None, 1, st.panel.colsum)
+        else:
+            self.be.mu_apply(st, st.num1, st.den1, 1, None)
+
+    def _half_step(self, st: StepBuf, csr):
+        self._numerator(st, csr)
+        self._denominator(st)
+        self._apply(st)
 
     def w_step(self):
         self._half_step(self.step_w, self.csr_w)
@@ -135,21 +155,28 @@ class SparseMU:
     def h_step(self):
         self._half_step(self.step_h, self.csr_h)
 
-    def divergence(self) -> float:
-        """V_norm + pos - neg (nmf.py:357, 397).  One host sync."""
+    def _launch_neg(self):
+        """loss_out = the sum over the stored entries (nmf.py:619, 626, 636): the O(nnz) term in HIP, one double partial per
+        four rows in loss_part.  Enqueued only."""
         rowptr, colidx, vals = self.csr_h
-        _capi.check(self.lib.nmfmu_sp_loss_neg(rowptr.data_ptr(), colidx.data_ptr(), vals.data_ptr(), self.fH.rows,
+        _capi.check(self.lib.nmfmu_sp_loss_neg(rowptr.data_ptr(), self._entries(colidx), self._entries(vals), self.fH.rows,
                                                self.fH.f.data_ptr(), self.fW.f.data_ptr(), self.rank, self.beta,
                                                self.loss_part.data_ptr(), self.loss_out.data_ptr(), self._s()),
                     'nmfmu_sp_loss_neg')
+
+    def _pos(self) -> float:
         if self.kl:      # pos = W.sum(0) . H.sum(0)
-            pos = float((self.fW.colsum[:self.rank].double() @ self.fH.colsum[:self.rank].double()).item())
-        elif self.generic:   # pos = sum (H W^T + eps)^beta / beta over every entry: the fused loss mode without a target
+            return float((self.fW.colsum[:self.rank].double() @ self.fH.colsum[:self.rank].double()).item())
+        if self.generic:   # pos = sum (H W^T + eps)^beta / beta over every entry: the fused loss mode without a target
             self.be.loss(self.step_h, self.dloss_part, self.dloss_out)
-            pos = float(self.dloss_out.item())
-        else:            # pos = 1/2 <H W^T W, H> = 1/2 sum(H^T H * W^T W)
-            for f, g in ((self.fH, self.gram), (self.fW, self.gram2)):
-                _capi.check(self.lib.nmfmu_gram(f.f.data_ptr(), f.rows, self.rank, self.gram_part.data_ptr(), g.data_ptr(),
-                                                self._s()), 'nmfmu_gram')
-            pos = 0.5 * float((self.gram.double() @ self.gram2.double()).item())
-        return self.v_norm + pos - float(self.loss_out.item())
+            return float(self.dloss_out.item())
+        # pos = 1/2 <H W^T W, H> = 1/2 sum(H^T H * W^T W)
+        for f, g in ((self.fH, self.gram), (self.fW, self.gram2)):
+            _capi.check(self.lib.nmfmu_gram(f.f.data_ptr(), f.rows, self.rank, self.gram_part.data_ptr(), g.data_ptr(),
+                                            self._s()), 'nmfmu_gram')
+        return 0.5 * float((self.gram.double() @ self.gram2.double()).item())
+
+    def divergence(self) -> float:
+        """V_norm + pos - neg (nmf.py:357, 397).  One host sync."""
+        self._launch_neg()
+        return self.v_norm + self._pos() - float(self.loss_out.item())

@@ -1982,6 +1982,22 @@ def test_fit_sparse_equals_dense(dev, beta, rank):
     assert rel_err(ms.W.data.cpu(), md.W.data.cpu()) < tol and rel_err(ms.H.data.cpu(), md.H.data.cpu()) < tol
 
 
+@pytest.mark.parametrize('beta', [1, 2])
+def test_sparse_fit_rank_above_128_against_oracle(dev, beta):
+    """Rank 200 (four rank slots per lane in the gather kernels) against the oracle's sparse fit at the file's bar: the
+    sparse path for beta in {1, 2} is fp32 throughout (the 2e-2 of test_fit_sparse_equals_dense is its bf16 dense side)."""
+    from oracle import mu_oracle as O
+    from torchnmf_amd.nmf import NMF
+    g = torch.Generator().manual_seed(1200 + beta)
+    Vd = torch.rand(500, 700, generator=g)
+    Vs = torch.where(Vd > 0.93, Vd, torch.zeros(())).to_sparse().coalesce()
+    W0, H0 = torch.randn(700, 200, generator=g).abs(), torch.randn(500, 200, generator=g).abs()
+    m = NMF(W=W0, H=H0).to(dev)
+    n = m.fit(Vs.to(dev), beta, NO_STOP, 5)
+    Wr, Hr, nr, _ = O.sp_fit(Vs.indices(), Vs.values(), (500, 700), W0, H0, beta, NO_STOP, 5)
+    assert n == nr and rel_err(m.W.data.cpu(), Wr) < TOL and rel_err(m.H.data.cpu(), Hr) < TOL
+
+
 def test_sparse_fit_errors(dev):
     from torchnmf_amd.nmf import NMF, NMFD
     V = torch.rand(30, 20)
