@@ -50,7 +50,9 @@ extern "C" {
                                9: nmfmu_kernel_family / nmfmu_choose_nsplit_for (round 6: beta == 1 at padded rank 256 with fp16 operands runs the
                                   software-pipelined one-wave-per-SIMD kernel, ONE workgroup per CU -- the split must know the kernel);
                                   nmfmu_step.stamps (in-kernel clock stamps in the product build); nmfmu_ubench_mfma_hbm2;
-                                  NMFMU_PREC_F16R (3-byte target) */
+                                  NMFMU_PREC_F16R (3-byte target);
+                                  still 9, purely additive: nmfmu_reconstruct_backward / nmfmu_reconstruct_backward_ws /
+                                  nmfmu_beta_div_grad (torch.autograd through NMF.forward and the divergences) */
 
 #define NMFMU_OK 0
 #define NMFMU_ERR_UNSUPPORTED (-2) /* rank / precision / beta combination not built */
@@ -316,6 +318,31 @@ int nmfmu_norms(const float* x, int64_t n, double* part, double* out, void* stre
  * fp32 masters with fp32 MFMA; out is row-major [owner.rows][panel.rows], ld elements per row. */
 int nmfmu_reconstruct(const float* owner, int m, const float* panel, int k, int rank, float* out, int64_t ld,
                       void* stream);
+
+/* nmfmu_reconstruct_backward: the two gradients of out = owner panel^T given g = d loss / d out (m x k fp32, ld >= k
+ * elements per row, read in place -- no transposed copy is made):
+ *   grad_owner[m][r] = sum_k g[m][k] panel[k][r]          grad_panel[k][r] = sum_m g[m][k] owner[m][r]
+ * Exact-fp32 MFMA like nmfmu_reconstruct; any m, k, rank >= 1.  Either output may be NULL and is then not computed (the
+ * factor it multiplies may be NULL with it).  Each half cuts its contraction into parts, one workgroup per (128 x 128 output
+ * tile, part); with more than one part the partial products go to slabs in ws and are summed in part order by a second
+ * kernel -- no floating-point atomics, results are bit-identical run to run.  Two launches of the product kernel when both
+ * outputs are wanted: g is read twice.
+ * Split rule (a pure function of the shape; rows / contraction = m / k for grad_owner, k / m for grad_panel):
+ *   tiles = ceil(rows / 128) * ceil(rank / 128);  stages = ceil(contraction / 32)
+ *   n     = max(1, min(ceil(512 / tiles), stages / 4, 64));  parts = ceil(stages / ceil(stages / n))
+ *   every part is ceil(stages / parts) * 32 contraction steps long, the last one possibly shorter.
+ * nmfmu_reconstruct_backward_ws returns the floats of scratch `ws` must hold for these outputs (0: ws may be NULL) and, when
+ * splits is not NULL, writes splits[0] = parts of grad_owner, splits[1] = parts of grad_panel (0 for a half not wanted). */
+int64_t nmfmu_reconstruct_backward_ws(int m, int k, int rank, int want_owner, int want_panel, int* splits);
+int nmfmu_reconstruct_backward(const float* g, int64_t ld, int m, int k, const float* owner, const float* panel, int rank,
+                               float* grad_owner, float* grad_panel, float* ws, void* stream);
+
+/* nmfmu_beta_div_grad: gx[i] = upstream[0] * d nmfmu_beta_div(x, y) / d x[i] over n fp32 elements; upstream is the 0-dim
+ * incoming gradient ON THE DEVICE (no host read).  eps as in metrics.py:6-96:
+ *   beta == 2: x - y     beta == 1: 1 - y / (x + eps)     beta == 0: 1 / (x + eps) - (y + eps) / (x + eps)^2
+ *   otherwise: (x + eps)^(beta - 1) - y' (x + eps)^(beta - 2), y' = y + eps for beta < 0 only.  y is a constant. */
+int nmfmu_beta_div_grad(const float* x, const float* y, int64_t n, float beta, const float* upstream, float* gx,
+                        void* stream);
 
 
 /* ---- convolutive NMF (NMFD, nmf.py:700-779) --------------------------------------------------------------------

@@ -48,10 +48,18 @@ int launch_checkpoint(const float* part, int n, const uint32_t* status, double* 
 int launch_beta_div(const float* x, const float* y, int64_t n, float beta, int kind, double* part, double* out,
                     hipStream_t s);
 int launch_mu_terms(const float* s, const float* v, int64_t n, float beta, int kind, float* gn, float* gp, hipStream_t st);
+int launch_beta_div_grad(const float* x, const float* y, int64_t n, float beta, int kind, const float* upstream, float* gx,
+                         hipStream_t st);
 int launch_trainer_update(float* f, int rows, int cols, const float* neg, const float* pos, float l1, float l2, float ortho,
                           float gamma, float* grad, hipStream_t st);
 int launch_norms(const float* x, int64_t n, double* part, double* out, hipStream_t s);
 int launch_reconstruct(const float* A, int M, const float* B, int K, int R, float* out, int64_t ld, hipStream_t s);
+// nmfmu_autograd.hip: backward of launch_reconstruct.  backward_nsplit is the split rule (parts of the contraction per
+// output tile, a pure function of the shape); ws holds the [nsplit][rows][R] slabs of the halves that are split.
+int backward_nsplit(int rows, int contraction, int rank);
+int64_t backward_ws_floats(int m, int k, int rank, bool want_owner, bool want_panel, int* splits);
+int launch_reconstruct_backward(const float* G, int64_t ld, int m, int k, const float* owner, const float* panel, int rank,
+                                float* grad_owner, float* grad_panel, float* ws, hipStream_t s);
 int launch_probe_mfma(const uint16_t* a, const uint16_t* b, float* d, hipStream_t s);
 int launch_probe_lds_dma(const uint32_t* src, uint32_t* dst, int n_dwords, hipStream_t s);
 int launch_ubench_mfma_hbm(const void* operands, size_t operand_bytes, int f16, const void* stream_src, int kib_per_tile,

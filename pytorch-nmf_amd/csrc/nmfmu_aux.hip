@@ -610,6 +610,47 @@ int launch_mu_terms(const float* s, const float* v, int64_t n, float beta, int k
   return (int)hipGetLastError();
 }
 
+// (1b) the gradient of metrics.beta_div(x, y, beta) with respect to x, times the 0-dim incoming gradient (read on the
+// device: no host sync), for torch.autograd -- metrics.py:6-96 differentiated, eps where the reference has it:
+//   beta == 2: x - y          beta == 1: 1 - y / (x + eps)          beta == 0: 1 / (x + eps) - (y + eps) / (x + eps)^2
+//   else     : (x + eps)^(beta-1) - y' (x + eps)^(beta-2),  y' = y + eps for beta < 0 only
+// One pass over 12 bytes per element: HBM bound, so the divisions are IEEE and the powers are powf (the hardware
+// log2 / exp2 pair loses |(beta - 1) log2 s| ulps, 46 of them at s = eps, beta = 3).
+template <int BETA>
+__global__ void __launch_bounds__(256) beta_div_grad_kernel(const float* __restrict__ x, const float* __restrict__ y, int64_t n,
+                                                            float beta, const float* __restrict__ upstream,
+                                                            float* __restrict__ gx) {
+  const float up = upstream[0];
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    float g;
+    if constexpr (BETA == kEuc) {
+      g = x[i] - y[i];
+    } else if constexpr (BETA == kKL) {
+      g = 1.f - y[i] / (x[i] + kEps);
+    } else if constexpr (BETA == kIS) {
+      const float s = x[i] + kEps;
+      g = 1.f / s - (y[i] + kEps) / (s * s);
+    } else {
+      const float s = x[i] + kEps;
+      const float yb = beta < 0.f ? y[i] + kEps : y[i];
+      g = powf(s, beta - 1.f) - yb * powf(s, beta - 2.f);
+    }
+    gx[i] = up * g;
+  }
+}
+
+int launch_beta_div_grad(const float* x, const float* y, int64_t n, float beta, int kind, const float* upstream, float* gx,
+                         hipStream_t st) {
+  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 4096));
+  switch (kind) {
+    case kKL: hipLaunchKernelGGL(beta_div_grad_kernel<kKL>, dim3(grid), dim3(256), 0, st, x, y, n, beta, upstream, gx); break;
+    case kEuc: hipLaunchKernelGGL(beta_div_grad_kernel<kEuc>, dim3(grid), dim3(256), 0, st, x, y, n, beta, upstream, gx); break;
+    case kIS: hipLaunchKernelGGL(beta_div_grad_kernel<kIS>, dim3(grid), dim3(256), 0, st, x, y, n, beta, upstream, gx); break;
+    default: hipLaunchKernelGGL(beta_div_grad_kernel<kGen>, dim3(grid), dim3(256), 0, st, x, y, n, beta, upstream, gx); break;
+  }
+  return (int)hipGetLastError();
+}
+
 // (2) trainer.py:93-112 on a plain row-major parameter [rows][cols]; one workgroup per row (row sum for the
 // orthogonality penalty in a fixed order)
 __global__ void __launch_bounds__(256) trainer_update_kernel(float* __restrict__ f, int cols, const float* __restrict__ neg,

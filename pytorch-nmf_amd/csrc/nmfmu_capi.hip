@@ -549,6 +549,26 @@ int nmfmu_reconstruct(const float* owner, int m, const float* panel, int k, int 
   return launch_reconstruct(owner, m, panel, k, rank, out, ld, S(stream));
 }
 
+int64_t nmfmu_reconstruct_backward_ws(int m, int k, int rank, int want_owner, int want_panel, int* splits) {
+  if (m <= 0 || k <= 0 || rank <= 0) return NMFMU_ERR_ARG;
+  return backward_ws_floats(m, k, rank, want_owner != 0, want_panel != 0, splits);
+}
+
+int nmfmu_reconstruct_backward(const float* g, int64_t ld, int m, int k, const float* owner, const float* panel, int rank,
+                               float* grad_owner, float* grad_panel, float* ws, void* stream) {
+  if (!g || m <= 0 || k <= 0 || rank <= 0 || ld < k) return NMFMU_ERR_ARG;
+  if ((grad_owner && !panel) || (grad_panel && !owner)) return NMFMU_ERR_ARG;
+  if (!ws && backward_ws_floats(m, k, rank, grad_owner != nullptr, grad_panel != nullptr, nullptr) > 0) return NMFMU_ERR_ARG;
+  return launch_reconstruct_backward(g, ld, m, k, owner, panel, rank, grad_owner, grad_panel, ws, S(stream));
+}
+
+int nmfmu_beta_div_grad(const float* x, const float* y, int64_t n, float beta, const float* upstream, float* gx,
+                        void* stream) {
+  if (!x || !y || !upstream || !gx || n < 0) return NMFMU_ERR_ARG;
+  if (n == 0) return NMFMU_OK;
+  return launch_beta_div_grad(x, y, n, beta, nmfmu_beta_kind(beta), upstream, gx, S(stream));
+}
+
 int nmfmu_timer_create(int n_events, void** timer) {
   if (n_events <= 0 || !timer) return NMFMU_ERR_ARG;
   Timer* t = new (std::nothrow) Timer;

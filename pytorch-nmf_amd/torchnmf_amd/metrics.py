@@ -3,7 +3,11 @@
 Reference: torchnmf/metrics.py:6-96.  ``input`` is the reconstruction, ``target``
 the data.  Each call launches one fused elementwise-reduction HIP kernel
 (``nmfmu_beta_div``) and returns a 0-dim float32 tensor on the inputs' device;
-there is no CPU path and no autograd (the fit loop never differentiates them).
+there is no CPU path.  The divergences are differentiable with respect to
+``input`` (``torch.autograd``, first order): when it requires grad the result
+carries a ``grad_fn`` whose backward is one elementwise HIP kernel
+(``nmfmu_beta_div_grad``).  ``target`` is always a constant: no gradient flows
+to it, whether or not it requires grad.
 """
 from __future__ import annotations
 
@@ -15,11 +19,7 @@ from . import _capi
 __all__ = ['kl_div', 'euclidean', 'is_div', 'beta_div', 'sparseness']
 
 
-def beta_div(input: Tensor, target: Tensor, beta: float = 2) -> Tensor:
-    """beta-divergence (metrics.py:60-96); beta = 2 / 1 / 0 are the Euclidean, KL and Itakura-Saito cases."""
-    if input.device.type != 'cuda' or target.device.type != 'cuda':
-        raise _capi.NmfmuError('beta_div: tensors must live on the ROCm device (no CPU fallback)')
-    assert input.shape == target.shape, 'input and target must have the same shape'
+def _beta_div_value(input: Tensor, target: Tensor, beta: float) -> Tensor:
     lib = _capi.load()
     x = input.detach().float().contiguous().reshape(-1)
     y = target.detach().float().contiguous().reshape(-1)
@@ -28,6 +28,41 @@ def beta_div(input: Tensor, target: Tensor, beta: float = 2) -> Tensor:
     _capi.check(lib.nmfmu_beta_div(x.data_ptr(), y.data_ptr(), x.numel(), float(beta), part.data_ptr(), out.data_ptr(),
                                    torch.cuda.current_stream().cuda_stream), 'nmfmu_beta_div')
     return out[0].float()
+
+
+class _BetaDivFn(torch.autograd.Function):
+    """The value from the same ``nmfmu_beta_div`` launch as without autograd; the gradient with respect to ``input`` from
+    ``nmfmu_beta_div_grad``, which reads the 0-dim incoming gradient on the device (no host sync)."""
+
+    @staticmethod
+    def forward(ctx, input, target, beta):
+        ctx.save_for_backward(input, target)
+        ctx.beta = float(beta)
+        return _beta_div_value(input, target, beta)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        input, target = ctx.saved_tensors
+        lib = _capi.load()
+        x = input.detach().float().contiguous().reshape(-1)
+        y = target.detach().float().contiguous().reshape(-1)
+        up = g.detach().float().reshape(1).contiguous()
+        gx = torch.empty_like(x)
+        _capi.check(lib.nmfmu_beta_div_grad(x.data_ptr(), y.data_ptr(), x.numel(), ctx.beta, up.data_ptr(), gx.data_ptr(),
+                                            torch.cuda.current_stream().cuda_stream), 'nmfmu_beta_div_grad')
+        return gx.reshape(input.shape).to(input.dtype), None, None
+
+
+def beta_div(input: Tensor, target: Tensor, beta: float = 2) -> Tensor:
+    """beta-divergence (metrics.py:60-96); beta = 2 / 1 / 0 are the Euclidean, KL and Itakura-Saito cases.
+    Differentiable with respect to ``input``; ``target`` is a constant."""
+    if input.device.type != 'cuda' or target.device.type != 'cuda':
+        raise _capi.NmfmuError('beta_div: tensors must live on the ROCm device (no CPU fallback)')
+    assert input.shape == target.shape, 'input and target must have the same shape'
+    if torch.is_grad_enabled() and input.requires_grad:
+        return _BetaDivFn.apply(input, target, beta)
+    return _beta_div_value(input, target, beta)
 
 
 def kl_div(input: Tensor, target: Tensor) -> Tensor:

@@ -10,8 +10,10 @@ ABI of ``include/nmfmu.h``; there is no CPU path (a CPU-resident module raises
 on ``forward`` / ``fit``).
 
 ``NMF2D`` / ``NMF3D`` (nmf.py:782-942) and sparse-COO targets of ``NMF.fit`` (nmf.py:351-398, 602-638) run on
-the same engines.  Out of scope: ``sparse_fit`` (Hoyer-projected gradient) and autograd through
-``forward``.
+the same engines.  ``NMF.forward`` / ``NMF.reconstruct`` are differentiable (``torch.autograd`` through an exact-fp32
+MFMA backward, ``nmfmu_reconstruct_backward``): ``beta_div(m(), V, beta).backward()`` and any ``torch.optim`` optimizer
+work as in the reference.  Out of scope: ``sparse_fit`` (Hoyer-projected gradient) and autograd
+through the convolutive ``forward`` (``NMFD`` / ``NMF2D`` / ``NMF3D``).
 """
 from __future__ import annotations
 
@@ -54,6 +56,71 @@ def _require_device(t: Tensor, what: str) -> None:
     if t.device.type != 'cuda':
         raise _capi.NmfmuError(f'{what}: tensors live on {t.device}; torchnmf_amd computes on an MI355X only -- move '
                                f'the module and its inputs with .cuda() (there is no CPU fallback)')
+
+
+def _reconstruct_forward(H: Tensor, W: Tensor) -> Tensor:
+    lib = _capi.load()
+    lead = tuple(H.shape[:-1])                       # F.linear accepts leading batch dimensions (nmf.py:693)
+    Hc = H.detach().float().reshape(-1, H.shape[-1]).contiguous()
+    Wc = W.detach().float().contiguous()
+    out = torch.empty(Hc.shape[0], Wc.shape[0], dtype=torch.float32, device=H.device)
+    _capi.check(lib.nmfmu_reconstruct(Hc.data_ptr(), Hc.shape[0], Wc.data_ptr(), Wc.shape[0], Hc.shape[1],
+                                      out.data_ptr(), out.stride(0), torch.cuda.current_stream().cuda_stream),
+                'nmfmu_reconstruct')
+    out = out.reshape(lead + (Wc.shape[0],))
+    return out if H.dtype == torch.float32 else out.to(H.dtype)      # (a module cast to another dtype answers in it)
+
+
+def reconstruct_backward_splits(m: int, k: int, rank: int):
+    """(parts of grad_owner's contraction, parts of grad_panel's) for an ``m x k`` incoming gradient: the split rule of
+    ``nmfmu_reconstruct_backward`` (include/nmfmu.h), a pure function of the shape."""
+    import ctypes
+    splits = (ctypes.c_int * 2)()
+    _capi.load().nmfmu_reconstruct_backward_ws(m, k, rank, 1, 1, splits)
+    return splits[0], splits[1]
+
+
+def _reconstruct_backward(G: Tensor, H: Tensor, W: Tensor, need_h: bool, need_w: bool):
+    """(grad_H | None, grad_W | None) of ``out = H @ W.T`` given ``G = d loss / d out``, in the inputs' shapes and dtypes.
+    ``G`` is read in place through its row stride; only a last stride other than 1 costs a copy."""
+    lib = _capi.load()
+    R, C = H.shape[-1], W.shape[0]
+    Hc = H.detach().float().reshape(-1, R).contiguous()
+    Wc = W.detach().float().contiguous()
+    N = Hc.shape[0]                                  # leading dimensions of H flattened: grad_W sums over all of them
+    G2 = G.detach().float().reshape(N, C)
+    if G2.stride(1) != 1 or (N > 1 and G2.stride(0) < C):
+        G2 = G2.contiguous()
+    ld = G2.stride(0) if N > 1 else C
+    gH = torch.empty(N, R, dtype=torch.float32, device=G2.device) if need_h else None
+    gW = torch.empty(C, R, dtype=torch.float32, device=G2.device) if need_w else None
+    n_ws = lib.nmfmu_reconstruct_backward_ws(N, C, R, int(need_h), int(need_w), None)
+    ws = torch.empty(n_ws, dtype=torch.float32, device=G2.device) if n_ws > 0 else None
+    _capi.check(lib.nmfmu_reconstruct_backward(G2.data_ptr(), ld, N, C, Hc.data_ptr(), Wc.data_ptr(), R,
+                                               gH.data_ptr() if need_h else None, gW.data_ptr() if need_w else None,
+                                               ws.data_ptr() if ws is not None else None,
+                                               torch.cuda.current_stream().cuda_stream), 'nmfmu_reconstruct_backward')
+    if need_h:
+        gH = gH.reshape(H.shape).to(H.dtype)
+    if need_w:
+        gW = gW.to(W.dtype)
+    return gH, gW
+
+
+class _ReconstructFn(torch.autograd.Function):
+    """``NMF.reconstruct`` with a device backward.  The forward is the same ``nmfmu_reconstruct`` launch as without autograd
+    (bit-identical output)."""
+
+    @staticmethod
+    def forward(ctx, H, W):
+        ctx.save_for_backward(H, W)
+        return _reconstruct_forward(H, W)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, G):
+        H, W = ctx.saved_tensors
+        return _reconstruct_backward(G, H, W, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
 
 
 class BaseComponent(nn.Module):
@@ -293,20 +360,17 @@ class NMF(BaseComponent):
 
     @staticmethod
     def reconstruct(H: Tensor, W: Tensor) -> Tensor:
-        """``H @ W.T`` (nmf.py:691-693) by an exact-fp32 MFMA kernel on the device."""
+        """``H @ W.T`` (nmf.py:691-693) by an exact-fp32 MFMA kernel on the device.
+
+        Differentiable like the reference's ``F.linear``: with grad mode on and ``H`` or ``W`` requiring grad the result
+        carries a ``grad_fn`` whose backward is one ``nmfmu_reconstruct_backward`` call (first order only).  Under
+        ``torch.no_grad()`` -- ``fit()``, ``BetaMu.step`` -- nothing is recorded."""
         _require_device(H, 'reconstruct')
         _require_device(W, 'reconstruct')
         assert H.dim() >= 2 and W.dim() == 2 and H.shape[-1] == W.shape[1]
-        lib = _capi.load()
-        lead = tuple(H.shape[:-1])                       # F.linear accepts leading batch dimensions (nmf.py:693)
-        Hc = H.detach().float().reshape(-1, H.shape[-1]).contiguous()
-        Wc = W.detach().float().contiguous()
-        out = torch.empty(Hc.shape[0], Wc.shape[0], dtype=torch.float32, device=H.device)
-        _capi.check(lib.nmfmu_reconstruct(Hc.data_ptr(), Hc.shape[0], Wc.data_ptr(), Wc.shape[0], Hc.shape[1],
-                                          out.data_ptr(), out.stride(0), torch.cuda.current_stream().cuda_stream),
-                    'nmfmu_reconstruct')
-        out = out.reshape(lead + (Wc.shape[0],))
-        return out if H.dtype == torch.float32 else out.to(H.dtype)      # (a module cast to another dtype answers in it)
+        if torch.is_grad_enabled() and (H.requires_grad or W.requires_grad):
+            return _ReconstructFn.apply(H, W)
+        return _reconstruct_forward(H, W)
 
     def _make_engine(self, V, beta, l1, l2, precision, group, allreduce=None):
         from .engine import DenseMU

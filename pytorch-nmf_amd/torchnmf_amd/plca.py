@@ -312,7 +312,7 @@ class PLCA(BaseComponent):
     def reconstruct(H: Tensor, W: Tensor, Z: Tensor) -> Tensor:
         """``H @ (W * Z).T`` (plca.py:371-373) on the device (exact-fp32 MFMA kernel of NMF.reconstruct)."""
         from .nmf import NMF
-        return NMF.reconstruct(H, W.detach() * Z.detach())
+        return NMF.reconstruct(H.detach(), W.detach() * Z.detach())      # (PLCA stays outside autograd)
 
     def _make_em(self, Vn, precision):
         assert Vn.dim() == 2 and Vn.shape == (self.H.shape[0], self.W.shape[0])
