@@ -29,6 +29,28 @@ Rounding points, as written in the sources (pytorch-nmf_amd/csrc):
 The four kernel families implement the same arithmetic up to fp32 evaluation order (v_fma_mix_f32 folds the fp16 target
 into the ratio, the fused epilogue multiplies by v_rcp_f32 where the apply kernel divides): no family rounds to a
 different operand value on purpose, so the emulation has no per-family branch.
+
+The beta == 2 path without the reconstruction (family 'xb': what fit() runs, DenseMU(allow_gram=True)) rounds elsewhere:
+
+* Gram matrix (nmfmu_gram.hip): G = P2^T P2 from the panel's 16-bit transposed image, products exact in fp32, fp32
+  accumulation (gram_partial_kernel :23-111, fixed-order sums in gram_finalize_kernel :117-163) -- ``gram_matrix`` is the
+  float64 value, the accumulation order is what ``gram_plan`` / ``gram_excess`` allow for.  The tail of gram_finalize_kernel (:166-193) turns
+  row r of the fp32 matrix into 16-bit hi / lo images times a power-of-two scale 2^ex[r] (row maximum at [2^9, 2^10)):
+  ``gram_images`` mirrors it bit for bit.
+* numerator (nmfmu_fused.h:805-880, ``xb_to_ops`` :379-393): X @ P2 with the stored target word as the operand (bf16 /
+  f16), or the fp32 target as an fp16 hi + lo pair against the one panel plane (f16x, ``XSPLIT``) -- the beta == 2
+  numerator of ``half_step``.
+* denominator (nmfmu_fused.h:918-1007): den[m][r] = (sum_q owner[m][q] (G_hi[r][q] + G_lo[r][q])) * scale[r], fp32
+  accumulation over 2 * R_PAD / 16 MFMAs, the scale multiplied onto the fp32 accumulator afterwards (:1001-1003).  The
+  OWNER operand is its 16-bit row-major image (``load_owner_frags`` :457-467, called at :938), never the fp32 master; the
+  Gram operand is the 16-bit image pair; the fp32 Gram matrix is an output of nmfmu_gram_panel that neither route reads
+  (nmfmu_capi.hip:435 passes no fp32 matrix).  Both routes -- the fused apply (``den_fused`` :925) and the split one
+  (``den_split`` :926, its tiles stored at :1154-1158) -- run these very lines, so they round the owner alike and the
+  emulation has NO branch between them.  The apply kernel's ``den_nslab`` branch (nmfmu_aux.hip:204-216) only reads
+  that ONE slab (dslab == 1: no sum over splits) and goes on with relu + eps as for every other beta.
+* ``nmfmu_xb_partial`` (nmfmu_capi.hip:420-424) passes no Gram images: ``slab_den`` is dropped (:140-141), ``den_split``
+  is false, and NOTHING forms a denominator -- the apply kernel has no product of its own (it only sums slabs), so the
+  whole of owner @ G is left to the caller, who must fill a denominator slab before nmfmu_mu_apply.
 """
 from __future__ import annotations
 
@@ -262,6 +284,100 @@ def apply(theta, num, den, beta: float, gamma: float, l1=0.0, l2=0.0, kl_den=Non
     return theta * mult
 
 
+# ---- beta == 2 without the reconstruction: Gram matrix, its images, the XB half-step ----------------------------------
+GRAM_MAX_CHUNKS = 256     # kGramMaxChunks (nmfmu_gram.hip)
+GRAM_TILES_PER_CHUNK = 4  # kGramTilesPerChunk
+# NMFMU_XB_NSTAGE (nmfmu_fused.h:195-197).  A library built with another value (make EXTRA=-DNMFMU_XB_NSTAGE=3) needs this
+# constant edited along with the build flag: the ring claims below describe the kernel only while the two agree.
+XB_NSTAGE = 4
+
+
+def xb_nstage(precision: str) -> int:
+    """FusedCfg::NSTAGE of the kModeXB instances (nmfmu_fused.h:198): ring stages of the X / panel streams -- three for the
+    fp32 target of 'f16x' (XF32), else NMFMU_XB_NSTAGE."""
+    return 3 if precision == 'f16x' else XB_NSTAGE
+
+
+def gram_matrix(B_img) -> np.ndarray:
+    """B_img^T B_img in float64; B_img = the panel's 16-bit image VALUES, padded rows and columns included."""
+    B = np.asarray(B_img, dtype=np.float64)
+    return B.T @ B
+
+
+def gram_images(G32, r_pad: int, f16: bool):
+    """Bit-exact mirror of the tail of gram_finalize_kernel (nmfmu_gram.hip:166-193) on the fp32 matrix [r_pad, r_pad]:
+    row maximum -> frexp -> ex - 10 (ex = 0 for a zero row and for a row whose maximum is not below 3e38), scale = 2^ex,
+    hi = round16(v 2^-ex), lo = round16(v 2^-ex - hi).  Returns (hi words, lo words: uint16 [r_pad, r_pad], scale fp32)."""
+    G = np.ascontiguousarray(np.asarray(G32, dtype=np.float32).reshape(r_pad, r_pad))
+    with np.errstate(invalid='ignore', over='ignore', under='ignore'):
+        m = np.fmax.reduce(np.fmax(G, np.float32(0.0)), axis=1)       # fmaxf drops NaN (an all-NaN row fails ``m > 0`` too)
+        ok = (m > 0) & (m < np.float32(3.0e38))
+        _, ex = np.frexp(np.where(ok, m, np.float32(1.0)))
+        ex = np.where(ok, ex.astype(np.int64) - 10, 0)
+        down = np.ldexp(np.float32(1.0), -ex).astype(np.float32)
+        scale = np.ldexp(np.float32(1.0), ex).astype(np.float32)
+        v = torch.from_numpy((G * down[:, None]).astype(np.float32))
+        dt = torch.float16 if f16 else torch.bfloat16
+        hi = v.to(dt)
+        lo = (v - hi.float()).to(dt)
+    words = lambda t: t.view(torch.int16).numpy().view(np.uint16).copy()
+    return words(hi), words(lo), scale
+
+
+def image_values(words, f16: bool) -> np.ndarray:
+    """float64 values of 16-bit image words."""
+    w = torch.from_numpy(np.ascontiguousarray(words).view(np.int16))
+    return w.view(torch.float16 if f16 else torch.bfloat16).double().numpy()
+
+
+def gram_plan(rows: int, r_pad: int) -> dict:
+    """Launch arithmetic of nmfmu_gram_panel (nmfmu_gram.hip:217-221) and the summation chain of an element of the fp32 matrix.
+
+    ``n_seq`` = the longest chain of sequential fp32 additions a product passes through: 16 inside its MFMA (K = 16 products
+    per instruction; their order is not documented, so the worst one is taken), 4 MFMA accumulations per 64-row tile x
+    ``per`` tiles in a chunk's accumulator (:59-65, :80-96), ceil(nchunk / ngrp) additions of chunk partials in one thread
+    group of the finalize (:132-149; the rounds of 16 and 8 add in the same order as the single ones), ngrp - 1 additions
+    of the groups (:152-157)."""
+    ktiles = pad_rows(rows) // KBK
+    nchunk = ktiles if ktiles <= GRAM_MAX_CHUNKS else -(-ktiles // GRAM_TILES_PER_CHUNK)
+    nchunk = min(nchunk, GRAM_MAX_CHUNKS)
+    per = -(-ktiles // nchunk)
+    ngrp = 256 // (r_pad // 4)
+    tiles = [max(0, min(ktiles, (c + 1) * per) - c * per) for c in range(nchunk)]
+    return dict(ktiles=ktiles, nchunk=nchunk, per=per, ngrp=ngrp, tiles=tiles,
+                n_seq=16 + 4 * per + -(-nchunk // ngrp) + ngrp - 1)
+
+
+def gram_excess(G32, ref, n_seq: int) -> float:
+    """max over the elements of |G32 - ref| / (n_seq 2^-24 ref): every term of an element is non-negative, so the standard
+    bound of a summation tree of depth n_seq holds relative to the element itself.  An element whose reference is zero
+    (padding) must be exactly zero; a non-finite element counts as inf.  The check is ``gram_excess(...) <= 1``."""
+    G = np.asarray(G32, dtype=np.float64)
+    ref = np.asarray(ref, dtype=np.float64)
+    bound = n_seq * 2.0 ** -24 * np.abs(ref)
+    diff = np.abs(G - ref)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        ratio = np.where(bound > 0, diff / bound, np.where(diff == 0, 0.0, np.inf))
+    return float(np.where(np.isfinite(G), ratio, np.inf).max())
+
+
+def xb_half_step(X, A_img, B_img, G_hi, G_lo, scale, precision: str, rounding=True):
+    """Numerator and denominator of one beta == 2 half-step on the Gram path, float64.
+
+    X: [m, k] fp32 target rows; A_img: [m, q] the owner's 16-bit image values; B_img: [k, q] the panel's; G_hi / G_lo:
+    [r, q] values of the Gram image planes (row r = column r of the matrix, carrying 2^-ex[r]); scale: [r] = 2^ex[r].
+    num = the beta == 2 numerator of ``half_step`` (stored word, or the fp16 hi + lo pair of 'f16x'); den[m][r] =
+    (sum_q A_img[m][q] (G_hi[r][q] + G_lo[r][q])) scale[r] -- the fused and the split epilogue alike (see the header).
+    (``half_step`` also forms the reconstruction path's m x k denominator on the way; it is discarded here.)
+    rounding=False: the plain algorithm (exact target; pass exact factors and G_hi = gram_matrix, G_lo = 0, scale = 1)."""
+    A = np.asarray(A_img, dtype=np.float64)
+    B = np.asarray(B_img, dtype=np.float64)
+    hs = half_step(X, A, B, 2.0, precision, A_img=(A, None), B_img=(B, None), rounding=rounding)
+    G = np.asarray(G_hi, dtype=np.float64) + np.asarray(G_lo, dtype=np.float64)
+    den = (A @ G.T) * np.asarray(scale, dtype=np.float64)[None, :]
+    return {'num': hs['num'], 'den': den, 'num_amb': hs['num_amb'], 'den_amb': 0.0}
+
+
 # ---- the contraction split (mirror of nmfmu_capi.hip) ----------------------------------------------------------------
 def pad_rows(n: int) -> int:
     return -(-n // ROW_PAD) * ROW_PAD
@@ -344,28 +460,51 @@ def elem_err(got, ref, allow=0.0) -> np.ndarray:
 
 
 # ---- the case matrix of tests/test_gpu_emulated_parity.py ---------------------------------------------------------------
-def half_step_plan(N: int, C: int, R: int, precision: str, beta: float, ncu: int, nsplit=None, block_rows=None):
-    """{'w': ..., 'h': ...}: the kernel family, tile height, split and per-split tiles each half-step runs with."""
+def half_step_plan(N: int, C: int, R: int, precision: str, beta: float, ncu: int, nsplit=None, block_rows=None,
+                   gram=False):
+    """{'w': ..., 'h': ...}: the kernel family, tile height, split and per-split tiles each half-step runs with.
+    gram: the engine was built with allow_gram -- beta == 2 runs family 'xb' (kModeXB, 128-row tiles; the four-wave
+    kernel's split rule, tiles per split not rounded: nmfmu_capi.hip:115)."""
     r_pad = pad_rank(R)
     plan = {}
     for which, (m, k) in (('w', (C, N)), ('h', (N, C))):
         m_pad, k_pad = pad_rows(m), pad_rows(k)
         br = block_rows or default_block_rows(r_pad, precision, beta)
         fam = kernel_family(r_pad, precision, beta, br)
+        if gram and beta_kind(beta) == 'euc':
+            assert br == 128 and precision in ('bf16', 'f16', 'f16x') and (precision != 'f16x' or r_pad <= 128)
+            fam = 'xb'
         ns = choose_nsplit(m_pad, k_pad, r_pad, precision, beta, br, ncu, nsplit)
         plan[which] = dict(M=m, K=k, m_pad=m_pad, k_pad=k_pad, block_rows=br, family=fam, nsplit=ns,
-                           tps_raw=tiles_per_split(k_pad, ns, fam)[0], tiles=split_tiles(k_pad, ns, fam), r_pad=r_pad)
+                           tps_raw=tiles_per_split(k_pad, ns, fam)[0], tiles=split_tiles(k_pad, ns, fam), r_pad=r_pad,
+                           nstage=xb_nstage(precision))
     return plan
 
 
 def claim_holds(claim: str, p: dict, R: int) -> bool:
     """Does one half-step's plan ``p`` reach the control flow ``claim`` names?"""
     t = p['tiles']
+    live = [x for x in t if x]
+    nst, rt = p['nstage'], p['r_pad'] // 32
+    xb = p['family'] == 'xb'
     return {
+        # family 'xb': the NSTAGE-deep ring of nmfmu_fused.h:805-880 and the denominator tiles of :918-1007 / :1154-1158
+        'ring_prologue_short': xb and any(x < nst - 1 for x in live),
+        'ring_rem1': xb and any(x % nst == 1 for x in live),
+        'ring_rem2': xb and any(x % nst == 2 for x in live),
+        'ring_rem3': xb and any(x % nst == 3 for x in live),
+        'ring_exact': xb and any(x % nst == 0 for x in live),
+        'den_tiles_shared': xb and p['nsplit'] > 1 and min(p['nsplit'], rt) > 1,
+        'den_tiles_fewer_splits_than_tiles': xb and 1 < p['nsplit'] < rt,
+        'den_more_splits_than_tiles': xb and p['nsplit'] > rt > 1,
+        'empty_split_owns_den_tile': xb and any(x == 0 and ks < min(p['nsplit'], rt) for ks, x in enumerate(t)),
+        'den_one_tile_owner': xb and p['nsplit'] > 1 and rt == 1,
+        'den_one_slab_unsplit': xb and p['r_pad'] == 256 and p['nsplit'] == 1,
+        'touched_prefetch': xb and p['nsplit'] == 1 and R == p['r_pad'] == 128 and p['M'] % 128 == 0,
         'empty_split': 0 in t,
         'short_last_split': len([x for x in t if x]) > 1 and 0 < [x for x in t if x][-1] < t[0],
         'odd_tps': p['nsplit'] > 1 and p['tps_raw'] % 2 == 1,
-        'fused_apply': p['nsplit'] == 1,
+        'fused_apply': p['nsplit'] == 1 and not (xb and p['r_pad'] > 128),
         'split': p['nsplit'] > 1,
         'one_group': t == [4],
         'several_groups': p['nsplit'] == 1 and t[0] > 4,
@@ -457,4 +596,108 @@ def make_problem(case, seed=None):
     if case['target'].startswith('scale'):
         s = float(case['target'][5:])
         V, W0, H0 = V * s, W0 * s ** 0.5, H0 * s ** 0.5
+    if case.get('family') == 'xb':
+        # rank columns of unlike magnitude (1, 2, 4, 1, ...): neighbouring rows of the Gram image then carry different
+        # power-of-two scales, so a scale applied to the wrong row shows (tests/test_mu_emulation.py, fault (b))
+        W0, H0 = W0 * xb_column_scales(R), H0 * xb_column_scales(R)
+    if case['target'] == 'fac30':          # factors x 30 (their Gram matrix leaves fp16's range), the target to match
+        V, W0, H0 = V * 900.0, W0 * 30.0, H0 * 30.0
+    elif case['target'] == 'zero_row':       # an all-zero owner row in either half-step: its numerator is exactly 0
+        V[min(3, N - 1), :] = 0.0
+        V[:, min(5, C - 1)] = 0.0
     return V, W0, H0
+
+
+# ---- the case matrices of tests/test_gpu_gram_emulated_parity.py -----------------------------------------------------
+def gram_cases():
+    """nmfmu_gram_panel: (rows, rank) x {f16, bf16}, with the launch arithmetic each is named for and ``n_seq``, the length
+    of the longest sequential fp32 addition chain (``gram_plan``), written out per case."""
+    shapes = [  # rows, rank, n_seq, what
+        (1, 1, 52, 'one live row, three all-zero tiles'),
+        (300, 24, 52, 'padded rank 32: RT = 1, idle waves; finalize with nchunk 8 < ngrp 32'),
+        (700, 64, 36, '12 one-tile chunks'),
+        (5000, 128, 37, '80 one-tile chunks'),
+        (300, 200, 25, 'padded rank 256, one tile per chunk'),
+        (16500, 100, 48, '260 tiles -> 65 chunks of 4: the even double-buffer loop'),
+        (16500, 256, 52, 'the rank-256 loop with 4 tiles per chunk; finalize with ngrp 4'),
+        (66000, 40, 67, '1032 tiles -> 256 chunks of 5 (odd loop), one 2-tile chunk, 49 empty chunks'),
+        (82000, 128, 79, '1284 tiles -> 6 per chunk, 42 empty chunks'),
+    ]
+    cases = []
+    for rows, rank, n_seq, what in shapes:
+        for prec in ('f16', 'bf16'):
+            cases.append(dict(id=f'{rows}x{rank}-{prec}', rows=rows, rank=rank, precision=prec, n_seq=n_seq, scale=1.0,
+                              what=what))
+    for sc in (200.0, 1e-3):   # Gram entries above 65504 (the row scale must keep hi finite) / far below 1
+        cases.append(dict(id=f'5000x128-f16-x{sc:g}', rows=5000, rank=128, precision='f16', n_seq=37, scale=sc,
+                          what='range'))
+    return cases
+
+
+def gram_problem(case):
+    """The factor of a Gram case, fp32 on the CPU."""
+    g = torch.Generator().manual_seed(case['rows'] * 3 + case['rank'])
+    return torch.randn(case['rows'], case['rank'], generator=g).abs() * (3.0 * case['scale'])
+
+
+def xb_column_scales(R: int) -> torch.Tensor:
+    return 2.0 ** (torch.arange(R) % 3).float()
+
+
+XB_PRECISIONS = ('bf16', 'f16', 'f16x')
+
+
+def xb_cases(ncu: int):
+    """beta == 2 on the Gram path (DenseMU(allow_gram=True)): dicts like ``parity_cases``.  The contraction axis is C in the H
+    half-step and N in the W half-step; k_pad is a multiple of 256, so tile counts come in fours, and a forced split is
+    clipped to ktiles // 4 -- the short axis of a case therefore runs the fused apply on 4 tiles."""
+    cases = []
+
+    def add(prec, N, C, R, nsplit, claims, target='rand'):
+        regs = (0.05, 0.05) if len(cases) % 3 == 0 else (0.0, 0.0)
+        claims = tuple(c for c in claims if not c.startswith('@')) + \
+            tuple(c[2:] for c in claims if c.startswith('@' + str(xb_nstage(prec))))
+        tag = f'xb-{prec}-{N}x{C}r{R}-ns{nsplit}' + (f'-{target}' if target != 'rand' else '') + ('-reg' if regs[0] else '')
+        cases.append(dict(id=tag, family='xb', precision=prec, beta=2.0, N=N, C=C, R=R, nsplit=nsplit, block_rows=None,
+                          stage='dma', regs=regs, target=target, claims=claims, sample=None))
+
+    # claims written '@4name' / '@3name' hold at NSTAGE 4 (bf16, f16) / 3 (f16x) only
+    for prec in XB_PRECISIONS:
+        # unsplit, 4 tiles: the fused apply with the Gram image from global memory (padded rank 32) and through LDS (64, 128)
+        for R in (24, 64, 100, 128):
+            add(prec, 200, 250, R, 1, ('fused_apply', 'ragged_m', 'ragged_k', '@4ring_exact', '@3ring_rem1')
+                + (('ragged_r',) if R in (24, 100) else ()))
+        add(prec, 130, 2300, 64, 8, ('ring_prologue_short', 'short_last_split', 'ring_rem1', 'den_tiles_shared',
+                                     'den_more_splits_than_tiles', '@3ring_rem2'))                 # [5]*7 + [1]
+        add(prec, 130, 2048, 100, 7, ('short_last_split', 'ring_rem2', '@4ring_prologue_short', '@4ring_rem1'))  # [5]*6 + [2]
+        add(prec, 130, 1792, 24, 6, ('short_last_split', 'den_one_tile_owner', '@4ring_rem3', '@3ring_exact'))   # [5]*5 + [3]
+        add(prec, 130, 2304, 128, 7, ('empty_split', 'den_tiles_shared', '@4ring_rem2', '@3ring_exact'))         # [6]*6 + [0]
+        add(prec, 1280, 130, 64, 3, ('short_last_split', '@4ring_rem3', '@4ring_rem2', '@3ring_rem1', '@3ring_exact'))  # [7, 7, 6]
+        add(prec, 1100, 300, 24, 4, ('den_one_tile_owner', 'ragged_r'))                            # [5]*4 | [4, 4]: nd = 1
+        add(prec, 520, 1100, 128, 2, ('den_tiles_shared', 'den_tiles_fewer_splits_than_tiles'))   # [10, 10] | [6, 6]
+        add(prec, 256, 384, 128, 1, ('fused_apply', 'touched_prefetch'))
+        add(prec, 129, 385, 100, 1, ('fused_apply', 'ragged_m', 'ragged_r'))                       # owner rows = 1 mod 128
+    for prec in ('f16', 'f16x'):
+        add(prec, 520, 1100, 128, 4, ('den_tiles_shared',))                                        # [5]*4 | [4, 4, 4]
+    for prec in ('bf16', 'f16'):
+        add(prec, 1, 1100, 64, 4, ('m1',))                                                         # M = 1, split; K = 1 in the W half-step
+        # padded rank 256 (RT = 8): one slab from an unsplit launch, fewer splits than rank tiles, more splits than rank tiles
+        add(prec, 300, 640, 200, 1, ('den_one_slab_unsplit', 'ragged_r'))
+        add(prec, 300, 1280, 200, 3, ('den_tiles_fewer_splits_than_tiles', 'den_tiles_shared'))   # tiles {0,3,6} {1,4,7} {2,5}
+        add(prec, 130, 2304, 200, 9, ('den_more_splits_than_tiles',))                              # [4]*9: ks = 8 owns no tile
+        # [6]*6 + [0] with nd = 7: the empty split skips the ring and still forms rank tile 6 of the denominator
+        add(prec, 130, 2304, 200, 7, ('empty_split', 'empty_split_owns_den_tile'))
+    add('f16x', 1, 300, 24, 1, ('m1', 'fused_apply'))
+    add('f16', 520, 1100, 128, 2, ('den_tiles_shared',), target='zeros')
+    add('f16', 384, 1100, 64, 3, ('split',), target='zero_row')
+    add('f16x', 200, 250, 64, 1, ('fused_apply',), target='zero_row')
+    add('f16', 384, 1100, 64, 3, ('split',), target='fac30')
+    add('f16', 256, 384, 128, 1, ('fused_apply',), target='fac30')
+    return cases
+
+
+# every claim of family 'xb', and the NSTAGE values it can be reached at
+XB_CLAIMS = {'ring_prologue_short': (3, 4), 'ring_rem1': (3, 4), 'ring_rem2': (3, 4), 'ring_rem3': (4,), 'ring_exact': (3, 4),
+             'den_tiles_shared': (3, 4), 'den_tiles_fewer_splits_than_tiles': (3, 4), 'den_one_slab_unsplit': (4,),
+             'empty_split': (3, 4), 'empty_split_owns_den_tile': (4,), 'short_last_split': (3, 4), 'fused_apply': (3, 4), 'ragged_m': (3, 4), 'ragged_k': (3, 4),
+             'ragged_r': (3, 4), 'm1': (3, 4)}

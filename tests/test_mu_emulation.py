@@ -179,3 +179,263 @@ def test_seeded_fault_one_rank_column(prefix):
     bad = ok['num'].copy()
     bad[:, 7] *= 1 + 1e-4
     assert E.elem_err(bad, ok['num'], ok['num_amb']).max() > E.TOL[c['precision']]
+
+
+# ---- beta == 2 without the reconstruction (family 'xb', tests/test_gpu_gram_emulated_parity.py) ---------------------
+@pytest.mark.parametrize('regs', [(0.0, 0.0), (0.1, 0.2)])
+def test_unrounded_xb_emulation_is_the_oracle(regs):
+    """rounding=False: owner @ (panel^T panel) and X @ panel followed by the apply are the reference's beta == 2 half-steps
+    (reconstruction + two backward products) in float64."""
+    l1, l2 = regs
+    V, W, H = _problem(70, 90, 13, 5, 2.0)
+    one = np.ones(13)
+    em = E.xb_half_step(V.t().numpy(), W.numpy(), H.numpy(), E.gram_matrix(H.numpy()), 0.0, one, 'f16x', rounding=False)
+    Wn = E.apply(W.numpy(), em['num'], em['den'], 2.0, 1.0, l1, l2)
+    Wr = O.nmf_w_step(V, W, H, 2.0, 1.0, l1, l2).numpy()
+    assert np.abs(Wn - Wr).max() <= 1e-12 * np.abs(Wr).max()
+    em = E.xb_half_step(V.numpy(), H.numpy(), Wn, E.gram_matrix(Wn), 0.0, one, 'f16x', rounding=False)
+    Hn = E.apply(H.numpy(), em['num'], em['den'], 2.0, 1.0, l1, l2)
+    Hr = O.nmf_h_step(V, torch.from_numpy(Wr), H, 2.0, 1.0, l1, l2).numpy()
+    assert np.abs(Hn - Hr).max() <= 1e-12 * np.abs(Hr).max()
+
+
+def test_gram_images_are_bit_exact():
+    """gram_images against an independent formulation of gram_finalize_kernel's tail: the exponent from the fp32 bit
+    pattern of the row maximum, bf16 by the integer round-to-nearest-even formula, fp16 by numpy's conversion."""
+    g = np.random.default_rng(11)
+    r_pad = 64
+    G = (g.random((r_pad, r_pad)) * 10.0 ** g.integers(-6, 9, (r_pad, 1))).astype(np.float32)
+    G[3] = 0.0                                   # zero row (padding): scale 1
+    G[4, :] = 1024.0                             # maximum an exact power of two: 0.5 * 2^11 -> scaled maximum 512
+    G[5, 7] = np.inf                             # the ``m < 3e38`` guard: ex = 0
+    G[6] = np.float32(3.2e38) * g.random(r_pad).astype(np.float32)
+    G[6, 0] = np.float32(3.2e38)             # finite, but not below 3e38: ex = 0 as well
+    G[7] *= np.float32(1e-30)
+    G[8, 1:] = 0.0                               # one entry carries the row
+    G[9] = np.float32(65504.0 * 37)
+    for f16 in (True, False):
+        hi, lo, scale = E.gram_images(G, r_pad, f16)
+        m = np.nanmax(np.where(np.isfinite(G), G, np.inf), axis=1).astype(np.float32)
+        expo = ((m.view(np.uint32) >> 23) & 0xff).astype(np.int64) - 127        # m = 1.f * 2^expo (normal numbers)
+        ok = (m > 0) & (m < np.float32(3.0e38))
+        ex = np.where(ok, expo + 1 - 10, 0)
+        assert np.array_equal(scale.astype(np.float64), 2.0 ** ex.astype(np.float64))
+        assert scale[3] == 1.0 and scale[5] == 1.0 and scale[6] == 1.0 and scale[4] == 2.0
+        with np.errstate(over='ignore', invalid='ignore'):
+            v = (G.astype(np.float64) * 2.0 ** -ex.astype(np.float64)[:, None]).astype(np.float32)   # exact: a power of two
+            fin = np.isfinite(v).all(axis=1) & (np.abs(v) < 6e4).all(axis=1)
+            assert fin.sum() >= r_pad - 2
+            if f16:
+                h = v.astype(np.float16)
+                l = (v - h.astype(np.float32)).astype(np.float16)
+                want_hi, want_lo = h.view(np.uint16), l.view(np.uint16)
+            else:
+                def bf(x):
+                    b = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32).astype(np.uint64)
+                    return ((b + 0x7fff + ((b >> 16) & 1)) >> 16).astype(np.uint16)
+                want_hi = bf(v)
+                hv = (want_hi.astype(np.uint32) << 16).view(np.float32)
+                want_lo = bf(v - hv)
+        assert np.array_equal(hi[fin], want_hi[fin]) and np.array_equal(lo[fin], want_lo[fin])
+        hv, lv = E.image_values(hi, f16), E.image_values(lo, f16)
+        assert 512.0 <= hv[4].max() < 1024.0 and all(512.0 <= hv[r].max() <= 1024.0 for r in (0, 1, 2, 7, 8, 9))
+        with np.errstate(invalid='ignore'):
+            rec = (hv + lv) * scale.astype(np.float64)[:, None]
+        sel = fin & ok
+        rel = 2.0 ** (-21 if f16 else -15)       # hi + lo: 22 (16) significant bits, less one where lo is subnormal / tiny
+        assert np.all(np.abs(rec[sel] - G[sel]) <= rel * m[sel, None].astype(np.float64))
+        assert not hv[3].any() and not lv[3].any()
+
+
+def test_every_xb_case_reaches_its_control_flow_on_256_cus():
+    """The Gram-path matrix: every case runs family 'xb' with the control flow it is named for, and every claim of the family
+    is reached at NSTAGE 4 (bf16, f16) and at NSTAGE 3 (f16x) wherever that instance can reach it."""
+    assert E.xb_nstage('f16x') == 3 and E.xb_nstage('f16') == E.xb_nstage('bf16') == 4
+    reached = {cl: set() for cl in E.XB_CLAIMS}
+    ids = set()
+    for c in E.xb_cases(256):
+        assert c['id'] not in ids and max(c['N'], c['C']) <= 2400
+        ids.add(c['id'])
+        assert c['precision'] != 'f16x' or E.pad_rank(c['R']) <= 128
+        plan = E.half_step_plan(c['N'], c['C'], c['R'], c['precision'], 2.0, 256, c['nsplit'], None, gram=True)
+        assert {plan['w']['family'], plan['h']['family']} == {'xb'}, c['id']
+        for cl in c['claims']:
+            assert any(E.claim_holds(cl, plan[w], c['R']) for w in plan), (c['id'], cl)
+        for cl in reached:
+            if any(E.claim_holds(cl, plan[w], c['R']) for w in plan):
+                reached[cl].add(E.xb_nstage(c['precision']))
+    for cl, want in E.XB_CLAIMS.items():
+        assert reached[cl] >= set(want), (cl, reached[cl])
+    assert sum(1 for c in E.xb_cases(256) if c['regs'][0] > 0) * 3 >= len(E.xb_cases(256)) - 2
+    # the split arithmetic of the shapes the matrix is built on
+    assert E.split_tiles(2304, 8, 'xb') == [5] * 7 + [1] and E.split_tiles(2048, 7, 'xb') == [5] * 6 + [2]
+    assert E.split_tiles(1792, 6, 'xb') == [5] * 5 + [3] and E.split_tiles(2304, 7, 'xb') == [6] * 6 + [0]
+    assert E.split_tiles(1280, 3, 'xb') == [7, 7, 6] and E.split_tiles(2304, 9, 'xb') == [4] * 9
+    # the Gram launches: chunks, tiles per chunk, and the chain length written into every case
+    for c in E.gram_cases():
+        assert E.gram_plan(c['rows'], E.pad_rank(c['rank']))['n_seq'] == c['n_seq'], c['id']
+    p = E.gram_plan(16500, 128)
+    assert (p['ktiles'], p['nchunk'], p['per']) == (260, 65, 4)
+    p = E.gram_plan(66000, 64)
+    assert (p['ktiles'], p['nchunk'], p['per']) == (1032, 256, 5) and sorted(set(p['tiles'])) == [0, 2, 5] and p['tiles'].count(0) == 49
+    p = E.gram_plan(82000, 128)
+    assert (p['ktiles'], p['nchunk'], p['per']) == (1284, 256, 6)
+
+
+# Seeded faults of the Gram path.  Each is applied to the emulation's output and must fail the check the GPU test asserts
+# (E.elem_err against E.TOL for numerator / denominator / master, E.gram_excess <= 1 for the fp32 matrix); ``old`` says
+# whether the bars of the older tests would have let it through (whole-factor relative norm < 1e-4, 5e-3 in bf16:
+# test_half_steps_beta2_without_reconstruction; Gram matrix norm < 2e-6: test_gram_panel_matches_fp32).
+OLD_BAR = {'f16': 1e-4, 'f16x': 1e-4, 'bf16': 5e-3}
+
+
+def _xb_state(N, C, R, prec, seed=3):
+    """H half-step (owner H [N, R], panel W [C, R]) as the GPU would hold it: images, Gram matrix in fp32, its images."""
+    g = torch.Generator().manual_seed(seed)
+    V = torch.rand(N, C, generator=g)
+    W = (torch.randn(C, R, generator=g).abs() + 0.05) * E.xb_column_scales(R)
+    H = (torch.randn(N, R, generator=g).abs() + 0.05) * E.xb_column_scales(R)
+    r_pad = E.pad_rank(R)
+    A = np.zeros((N, r_pad))
+    A[:, :R] = E.round_op(H.numpy(), prec)
+    B = np.zeros((E.pad_rows(C), r_pad))
+    B[:C, :R] = E.round_op(W.numpy(), prec)
+    G32 = E.gram_matrix(B).astype(np.float32)
+    f16 = prec in E.F16_OPS
+    hi, lo, scale = E.gram_images(G32, r_pad, f16)
+    return dict(X=V.numpy(), A=A, B=B, W=W.numpy(), H=H.numpy(), G32=G32, hi=E.image_values(hi, f16), lo=E.image_values(lo, f16),
+                scale=scale.astype(np.float64), prec=prec, R=R, C=C, r_pad=r_pad)
+
+
+def _xb_em(s, **kw):
+    a = dict(X=s['X'], A=s['A'], B=s['B'][:s['C']], hi=s['hi'], lo=s['lo'], scale=s['scale'])
+    a.update(kw)
+    return E.xb_half_step(a['X'], a['A'], a['B'], a['hi'], a['lo'], a['scale'], s['prec'])
+
+
+def _xb_verdict(s, ok, bad, name, expect_old_pass):
+    """new check: per element, numerator / denominator / master against E.TOL; old bar: relative norm of the new factor."""
+    R, tol = s['R'], E.TOL[s['prec']]
+    theta = s['H'].astype(np.float64)
+    ref = E.apply(theta, ok['num'][:, :R], ok['den'][:, :R], 2.0, 1.0)
+    got = E.apply(theta, bad['num'][:, :R], bad['den'][:, :R], 2.0, 1.0)
+    new = max(E.elem_err(bad['num'][:, :R], ok['num'][:, :R]).max(), E.elem_err(bad['den'][:, :R], ok['den'][:, :R]).max())
+    master = E.elem_err(got, ref).max()
+    finite = np.isfinite(got).all()
+    old = float(np.linalg.norm(got - ref) / np.linalg.norm(ref)) if finite else float('inf')
+    old_pass = old < OLD_BAR[s['prec']]
+    print(f'fault {name}: fails the new check (slab {new:.2e}, master {master:.2e} > {tol:.1e}); '
+          f'{"passes" if old_pass else "fails"} the old norm bar ({old:.2e} vs {OLD_BAR[s["prec"]]:.0e})')
+    assert new > tol and master > tol, (name, new, master)
+    assert old_pass == expect_old_pass, (name, old)
+
+
+@pytest.mark.parametrize('prec', ['f16', 'bf16'])
+def test_seeded_fault_gram_lo_plane_dropped(prec):
+    """(a) the lo plane of the Gram image lost: a 2^-12 (fp16) / 2^-9 (bf16) effect on the matrix, below the old norm bar."""
+    s = _xb_state(300, 1100, 100, prec)
+    _xb_verdict(s, _xb_em(s), _xb_em(s, lo=np.zeros_like(s['lo'])), f'(a) lo plane dropped, {prec}', True)
+
+
+@pytest.mark.parametrize('kind', ['not multiplied back', 'neighbouring row'])
+def test_seeded_fault_gram_row_scale(kind):
+    """(b) one row's scale not multiplied back / taken from the neighbouring row: one denominator column."""
+    s = _xb_state(300, 1100, 100, 'f16')
+    scale = s['scale'].copy()
+    r = next(i for i in range(s['R'] - 1) if scale[i] != scale[i + 1]) if kind == 'neighbouring row' else 17
+    scale[r] = scale[r + 1] if kind == 'neighbouring row' else 1.0
+    assert scale[r] != s['scale'][r]
+    _xb_verdict(s, _xb_em(s), _xb_em(s, scale=scale), f'(b) scale of row {r} {kind}', False)
+
+
+def _gram_verdict(name, G32, ref, n_seq, expect_old_pass):
+    ex = E.gram_excess(G32, ref, n_seq)
+    old = float(np.linalg.norm(G32.astype(np.float64) - ref) / np.linalg.norm(ref))
+    print(f'fault {name}: fails the new check ({ex:.2e} x the n_seq = {n_seq} bound); '
+          f'{"passes" if old < 2e-6 else "fails"} the old Gram norm bar ({old:.2e} vs 2e-06)')
+    assert ex > 1.0, (name, ex)
+    assert (old < 2e-6) == expect_old_pass, (name, old)
+
+
+def _gram_case(cid):
+    c = next(c for c in E.gram_cases() if c['id'] == cid)
+    rows, rank = c['rows'], c['rank']
+    r_pad = E.pad_rank(rank)
+    B = np.zeros((E.pad_rows(rows), r_pad))
+    B[:rows, :rank] = E.round_op(E.gram_problem(c).numpy(), c['precision'])
+    return c, B, E.gram_plan(rows, r_pad)
+
+
+def test_seeded_fault_last_short_gram_chunk_dropped():
+    """(c) the 2-tile chunk behind 206 chunks of 5 contributes nothing: 80 of 66000 rows."""
+    c, B, plan = _gram_case('66000x40-f16')
+    ref = E.gram_matrix(B)
+    assert E.gram_excess(ref.astype(np.float32), ref, c['n_seq']) <= 1.0      # the correctly rounded matrix passes
+    last = max(i for i, t in enumerate(plan['tiles']) if t)
+    assert plan['tiles'][last] == 2
+    cut = last * plan['per'] * E.KBK
+    _gram_verdict('(c) last, short Gram chunk dropped', E.gram_matrix(B[:cut]).astype(np.float32), ref, c['n_seq'], False)
+
+
+def test_seeded_fault_padded_panel_row_in_the_gram():
+    """(d) one padded row of the image holds a stale copy of a live row: in the Gram matrix, and in the denominator."""
+    c, B, plan = _gram_case('300x24-f16')
+    ref = E.gram_matrix(B)
+    Bp = B.copy()
+    Bp[c['rows'] + 5] = B[0]
+    _gram_verdict('(d) padded panel row non-zero (Gram matrix)', E.gram_matrix(Bp).astype(np.float32), ref, c['n_seq'], False)
+    s = _xb_state(300, 1100, 100, 'f16')
+    Bp = s['B'].copy()
+    Bp[s['C'] + 5] = s['B'][0]
+    hi, lo, scale = E.gram_images(E.gram_matrix(Bp).astype(np.float32), s['r_pad'], True)
+    bad = _xb_em(s, hi=E.image_values(hi, True), lo=E.image_values(lo, True), scale=scale.astype(np.float64))
+    _xb_verdict(s, _xb_em(s), bad, '(d) padded panel row non-zero (denominator)', False)
+
+
+def test_seeded_fault_denominator_tile_unwritten():
+    """(e) one 32-column rank tile of the ONE denominator slab left unwritten: the slab's NaN poison stays.  (The variant
+    "the same tile written by two workgroups" is left out: both compute the same product from the same operands in the
+    same order, so the slab holds the right bits either way -- a waste of time, not a wrong value, and invisible in one slab.)"""
+    s = _xb_state(300, 1100, 100, 'f16')
+    ok = _xb_em(s)
+    bad = dict(ok, den=ok['den'].copy())
+    bad['den'][128:256, 64:96] = np.nan
+    _xb_verdict(s, ok, bad, '(e) rank tile 2 of row block 1 unwritten', False)
+
+
+def test_seeded_fault_last_tile_of_a_rem1_split_dropped():
+    """(f) the last tile of a split with nt % NSTAGE == 1 (the ring's one-tile remainder) missing from the numerator."""
+    c = next(c for c in E.xb_cases(256) if c['id'].startswith('xb-f16-130x2300r64-ns8'))
+    tiles = E.half_step_plan(c['N'], c['C'], c['R'], 'f16', 2.0, 256, c['nsplit'], None, gram=True)['h']['tiles']
+    assert tiles == [5] * 7 + [1] and tiles[0] % E.xb_nstage('f16') == 1
+    s = _xb_state(130, 2300, 64, 'f16')
+    X = s['X'].copy()
+    X[:, 4 * E.KBK:5 * E.KBK] = 0.0               # the fifth tile of split 0
+    _xb_verdict(s, _xb_em(s), dict(_xb_em(s), num=_xb_em(s, X=X)['num']), '(f) tile 4 of split 0 dropped', False)
+
+
+@pytest.mark.parametrize('prec', ['f16', 'bf16'])
+def test_seeded_fault_gram_from_the_fp32_master(prec):
+    """(g) the Gram matrix formed from the fp32 master instead of the 16-bit image: caught in the fp32 matrix itself (where
+    the old 2e-6 norm bar is blind to it only for very long panels) and in the denominator; far below the old factor bar."""
+    c, B, plan = _gram_case('700x64-' + prec)
+    F = np.zeros_like(B)
+    F[:c['rows'], :c['rank']] = E.gram_problem(c).numpy()
+    _gram_verdict(f'(g) Gram from the fp32 master, {prec} (Gram matrix)', E.gram_matrix(F).astype(np.float32), E.gram_matrix(B),
+                  c['n_seq'], False)
+    s = _xb_state(1100, 130, 64, prec)
+    F = np.zeros_like(s['B'])
+    F[:s['C'], :s['R']] = s['W']
+    f16 = prec == 'f16'
+    hi, lo, scale = E.gram_images(E.gram_matrix(F).astype(np.float32), s['r_pad'], f16)
+    bad = _xb_em(s, hi=E.image_values(hi, f16), lo=E.image_values(lo, f16), scale=scale.astype(np.float64))
+    _xb_verdict(s, _xb_em(s), bad, f'(g) Gram from the fp32 master, {prec} (denominator)', True)
+
+
+def test_seeded_fault_owner_fragments_of_the_neighbouring_wave():
+    """(h) the denominator of one wave's 32 rows formed from the owner fragments of the wave next to it."""
+    s = _xb_state(300, 1100, 100, 'f16')
+    ok = _xb_em(s)
+    bad = dict(ok, den=ok['den'].copy())
+    bad['den'][32:64] = ok['den'][0:32]
+    _xb_verdict(s, ok, bad, '(h) owner fragments of wave 0 in wave 1', False)
