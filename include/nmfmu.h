@@ -52,7 +52,8 @@ extern "C" {
                                   nmfmu_step.stamps (in-kernel clock stamps in the product build); nmfmu_ubench_mfma_hbm2;
                                   NMFMU_PREC_F16R (3-byte target);
                                   still 9, purely additive: nmfmu_reconstruct_backward / nmfmu_reconstruct_backward_ws /
-                                  nmfmu_beta_div_grad (torch.autograd through NMF.forward and the divergences) */
+                                  nmfmu_beta_div_grad (torch.autograd through NMF.forward and the divergences);
+                                  nmfmu_conv_backward / nmfmu_conv_backward_ws (the same through NMFD / NMF2D / NMF3D.forward) */
 
 #define NMFMU_OK 0
 #define NMFMU_ERR_UNSUPPORTED (-2) /* rank / precision / beta combination not built */
@@ -344,6 +345,27 @@ int nmfmu_reconstruct_backward(const float* g, int64_t ld, int m, int k, const f
 int nmfmu_beta_div_grad(const float* x, const float* y, int64_t n, float beta, const float* upstream, float* gx,
                         void* stream);
 
+/* nmfmu_conv_backward: the two gradients of the convolutive reconstruction (NMFD / NMF2D / NMF3D.reconstruct, nmf.py:776-779 /
+ * 857-860 / 937-940: F.convNd(H, W.flip(..), padding = T - 1)) given g = d loss / d out.  ndim = 1..3 shift axes, lh / taps hold
+ * ndim entries (outermost axis first), l_a = lh_a + taps_a - 1.  All tensors fp32, contiguous:
+ *   g (batch, channels, *l)     w (channels, rank, *taps)     h (batch, rank, *lh)
+ *   grad_h[b][r][j] = sum_c sum_t w[c][r][t] g[b][c][j + t]          grad_w[c][r][t] = sum_b sum_j g[b][c][j + t] h[b][r][j]
+ * written straight into the layouts of h and w.  Exact-fp32 MFMA like nmfmu_reconstruct_backward.  No unfolded operand is built:
+ * with goff(x) = (x_0 l_1 + x_1) l_2 + x_2 the element g[b][c][j + t] lies at (b channels + c) prod(l) + goff(j) + goff(t), and
+ * the kernel fetches it with that index while staging to LDS.  Either output may be NULL and is then not computed (the factor
+ * it multiplies -- w for grad_h, h for grad_w -- may be NULL with it); the other output is bit-equal to the both-outputs call.
+ * Each half cuts its contraction into parts by the split rule of nmfmu_reconstruct_backward with
+ *   grad_h: rows = batch prod(lh), contraction = channels prod(taps)      grad_w: rows = channels prod(taps), contraction = batch prod(lh)
+ * (the rank tile is 32 wide for rank <= 32 and 128 wide above, so ceil(rank / 128) counts its tiles too), one workgroup per
+ * (128 rows, rank tile, part); with more than one part the partial products go to slabs [parts][output] in ws -- grad_h's
+ * first -- and are summed in part order: no floating-point atomics, bit-identical run to run.  batch prod(lh) and
+ * channels prod(taps) must not exceed 2^30 (NMFMU_ERR_ARG).
+ * nmfmu_conv_backward_ws (host only) returns the floats `ws` must hold (0: ws may be NULL) and, when splits is not NULL, writes
+ * splits[0] = parts of grad_h, splits[1] = parts of grad_w (0 for a half not wanted). */
+int64_t nmfmu_conv_backward_ws(int batch, int channels, int rank, int ndim, const int32_t* lh, const int32_t* taps, int want_h,
+                               int want_w, int* splits);
+int nmfmu_conv_backward(const float* g, const float* w, const float* h, int batch, int channels, int rank, int ndim,
+                        const int32_t* lh, const int32_t* taps, float* grad_h, float* grad_w, float* ws, void* stream);
 
 /* ---- convolutive NMF (NMFD, nmf.py:700-779) --------------------------------------------------------------------
  * NMFD is dense NMF on unfolded operands with effective rank R*T: with W (C,R,T) viewed as Wm (C x R*T) and

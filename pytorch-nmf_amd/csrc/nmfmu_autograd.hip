@@ -153,6 +153,12 @@ __global__ void __launch_bounds__(256) slab_sum_kernel(const float* __restrict__
   }
 }
 
+int launch_slab_sum(const float* slab, int nslab, int64_t plane, float* out, hipStream_t s) {
+  const int rgrid = (int)std::min<int64_t>((plane + 255) / 256, 2048);
+  hipLaunchKernelGGL(slab_sum_kernel, dim3(rgrid), dim3(256), 0, s, slab, nslab, plane, out);
+  return (int)hipGetLastError();
+}
+
 static int backward_half(bool trans, const float* G, int64_t ld, int rows, int C, const float* B, int R, float* out,
                          float* slab, hipStream_t s) {
   const int nsplit = backward_nsplit(rows, C, R);
@@ -165,10 +171,7 @@ static int backward_half(bool trans, const float* G, int64_t ld, int rows, int C
     hipLaunchKernelGGL(reconstruct_backward_kernel<false>, grid, dim3(256), 0, s, G, ld, rows, C, B, R, part_len, dst);
   int e = (int)hipGetLastError();
   if (e || nsplit == 1) return e;
-  const int64_t plane = (int64_t)rows * R;
-  const int rgrid = (int)std::min<int64_t>((plane + 255) / 256, 2048);
-  hipLaunchKernelGGL(slab_sum_kernel, dim3(rgrid), dim3(256), 0, s, slab, nsplit, plane, out);
-  return (int)hipGetLastError();
+  return launch_slab_sum(slab, nsplit, (int64_t)rows * R, out, s);
 }
 
 int64_t backward_ws_floats(int m, int k, int rank, bool want_owner, bool want_panel, int* splits) {

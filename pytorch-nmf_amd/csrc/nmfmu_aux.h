@@ -57,9 +57,19 @@ int launch_reconstruct(const float* A, int M, const float* B, int K, int R, floa
 // nmfmu_autograd.hip: backward of launch_reconstruct.  backward_nsplit is the split rule (parts of the contraction per
 // output tile, a pure function of the shape); ws holds the [nsplit][rows][R] slabs of the halves that are split.
 int backward_nsplit(int rows, int contraction, int rank);
+int backward_part_len(int contraction, int nsplit);
+// out[i] = ((slab[0][i] + slab[1][i]) + ...) over `plane` floats: slab_sum_kernel, parts added in part order
+int launch_slab_sum(const float* slab, int nslab, int64_t plane, float* out, hipStream_t s);
 int64_t backward_ws_floats(int m, int k, int rank, bool want_owner, bool want_panel, int* splits);
 int launch_reconstruct_backward(const float* G, int64_t ld, int m, int k, const float* owner, const float* panel, int rank,
                                 float* grad_owner, float* grad_panel, float* ws, hipStream_t s);
+// nmfmu_conv_autograd.hip: backward of the convolutive reconstruction (NMFD / NMF2D / NMF3D), 1..3 shift axes.  Same split rule
+// (rows = the output's long axis: B prod(lh) for grad_h, C prod(taps) for grad_w; contraction = the other one) and slab scheme.
+// Both return -1 for sizes that are not positive or do not fit the kernel's 32-bit flattened axes (2^30).
+int64_t conv_backward_ws_floats(int batch, int channels, int rank, int ndim, const int32_t* lh, const int32_t* taps, bool want_h,
+                                bool want_w, int* splits);
+int launch_conv_backward(const float* G, const float* W, const float* H, int batch, int channels, int rank, int ndim,
+                         const int32_t* lh, const int32_t* taps, float* grad_h, float* grad_w, float* ws, hipStream_t st);
 int launch_probe_mfma(const uint16_t* a, const uint16_t* b, float* d, hipStream_t s);
 int launch_probe_lds_dma(const uint32_t* src, uint32_t* dst, int n_dwords, hipStream_t s);
 int launch_ubench_mfma_hbm(const void* operands, size_t operand_bytes, int f16, const void* stream_src, int kib_per_tile,

@@ -562,6 +562,20 @@ int nmfmu_reconstruct_backward(const float* g, int64_t ld, int m, int k, const f
   return launch_reconstruct_backward(g, ld, m, k, owner, panel, rank, grad_owner, grad_panel, ws, S(stream));
 }
 
+int64_t nmfmu_conv_backward_ws(int batch, int channels, int rank, int ndim, const int32_t* lh, const int32_t* taps, int want_h,
+                               int want_w, int* splits) {
+  const int64_t n = conv_backward_ws_floats(batch, channels, rank, ndim, lh, taps, want_h != 0, want_w != 0, splits);
+  return n < 0 ? NMFMU_ERR_ARG : n;
+}
+
+int nmfmu_conv_backward(const float* g, const float* w, const float* h, int batch, int channels, int rank, int ndim,
+                        const int32_t* lh, const int32_t* taps, float* grad_h, float* grad_w, float* ws, void* stream) {
+  if (!g || (!grad_h && !grad_w) || (grad_h && !w) || (grad_w && !h)) return NMFMU_ERR_ARG;
+  const int64_t n = conv_backward_ws_floats(batch, channels, rank, ndim, lh, taps, grad_h != nullptr, grad_w != nullptr, nullptr);
+  if (n < 0 || (n > 0 && !ws)) return NMFMU_ERR_ARG;
+  return launch_conv_backward(g, w, h, batch, channels, rank, ndim, lh, taps, grad_h, grad_w, ws, S(stream));
+}
+
 int nmfmu_beta_div_grad(const float* x, const float* y, int64_t n, float beta, const float* upstream, float* gx,
                         void* stream) {
   if (!x || !y || !upstream || !gx || n < 0) return NMFMU_ERR_ARG;

@@ -118,6 +118,11 @@ SIGNATURES = {
     'nmfmu_reconstruct_backward_ws': (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     'nmfmu_reconstruct_backward': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'nmfmu_conv_backward_ws': (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                          C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    'nmfmu_conv_backward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]),
     'nmfmu_beta_div_grad': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     'nmfmu_gemm': (C.c_int, [C.POINTER(GemmDesc), C.c_int, C.c_void_p]),
     'nmfmu_gemm_window_staged': (C.c_int, [C.POINTER(GemmDesc), C.c_int]),

@@ -12,8 +12,8 @@ on ``forward`` / ``fit``).
 ``NMF2D`` / ``NMF3D`` (nmf.py:782-942) and sparse-COO targets of ``NMF.fit`` (nmf.py:351-398, 602-638) run on
 the same engines.  ``NMF.forward`` / ``NMF.reconstruct`` are differentiable (``torch.autograd`` through an exact-fp32
 MFMA backward, ``nmfmu_reconstruct_backward``): ``beta_div(m(), V, beta).backward()`` and any ``torch.optim`` optimizer
-work as in the reference.  Out of scope: ``sparse_fit`` (Hoyer-projected gradient) and autograd
-through the convolutive ``forward`` (``NMFD`` / ``NMF2D`` / ``NMF3D``).
+work as in the reference.  The convolutive ``forward`` (``NMFD`` / ``NMF2D`` / ``NMF3D``) is differentiable the same way
+(``nmfmu_conv_backward``).  Out of scope: ``sparse_fit`` (Hoyer-projected gradient).
 """
 from __future__ import annotations
 
@@ -121,6 +121,57 @@ class _ReconstructFn(torch.autograd.Function):
     def backward(ctx, G):
         H, W = ctx.saved_tensors
         return _reconstruct_backward(G, H, W, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+
+
+def conv_backward_splits(H_shape, W_shape):
+    """(parts of grad_H's contraction, parts of grad_W's) for factors of these shapes: the split rule of
+    ``nmfmu_conv_backward`` (include/nmfmu.h), a pure function of the shape."""
+    import ctypes
+    nd = len(H_shape) - 2
+    splits = (ctypes.c_int * 2)()
+    _capi.load().nmfmu_conv_backward_ws(H_shape[0], W_shape[0], H_shape[1], nd, (ctypes.c_int32 * nd)(*H_shape[2:]),
+                                        (ctypes.c_int32 * nd)(*W_shape[2:]), 1, 1, splits)
+    return splits[0], splits[1]
+
+
+def _conv_reconstruct_backward(G: Tensor, H: Tensor, W: Tensor, need_h: bool, need_w: bool):
+    """(grad_H | None, grad_W | None) of the convolutive reconstruction given ``G = d loss / d out``, in the inputs' shapes
+    and dtypes: one ``nmfmu_conv_backward`` call.  A contiguous fp32 ``G`` is read in place; anything else is copied once."""
+    import ctypes
+    lib = _capi.load()
+    Hc, Wc = H.detach().float().contiguous(), W.detach().float().contiguous()
+    Gc = G.detach().float().contiguous()
+    nd = Hc.dim() - 2
+    B, R, Cc = Hc.shape[0], Hc.shape[1], Wc.shape[0]
+    lh, taps = (ctypes.c_int32 * nd)(*Hc.shape[2:]), (ctypes.c_int32 * nd)(*Wc.shape[2:])
+    assert tuple(Gc.shape) == (B, Cc) + tuple(a + t - 1 for a, t in zip(Hc.shape[2:], Wc.shape[2:]))
+    gH = torch.empty_like(Hc) if need_h else None
+    gW = torch.empty_like(Wc) if need_w else None
+    n_ws = lib.nmfmu_conv_backward_ws(B, Cc, R, nd, lh, taps, int(need_h), int(need_w), None)
+    _capi.check(min(n_ws, 0), 'nmfmu_conv_backward_ws')
+    ws = torch.empty(n_ws, dtype=torch.float32, device=Gc.device) if n_ws > 0 else None
+    _capi.check(lib.nmfmu_conv_backward(Gc.data_ptr(), Wc.data_ptr(), Hc.data_ptr(), B, Cc, R, nd, lh, taps,
+                                        gH.data_ptr() if need_h else None, gW.data_ptr() if need_w else None,
+                                        ws.data_ptr() if ws is not None else None,
+                                        torch.cuda.current_stream().cuda_stream), 'nmfmu_conv_backward')
+    return (gH.to(H.dtype) if need_h else None), (gW.to(W.dtype) if need_w else None)
+
+
+class _ConvReconstructFn(torch.autograd.Function):
+    """``NMFD / NMF2D / NMF3D.reconstruct`` with a device backward.  The forward is ``nmfd_engine.reconstruct`` itself: the
+    same launches as without autograd (bit-identical output)."""
+
+    @staticmethod
+    def forward(ctx, H, W):
+        from .nmfd_engine import reconstruct as _recon
+        ctx.save_for_backward(H, W)
+        return _recon(H, W)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, G):
+        H, W = ctx.saved_tensors
+        return _conv_reconstruct_backward(G, H, W, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
 
 
 class BaseComponent(nn.Module):
@@ -430,7 +481,17 @@ class NMFD(BaseComponent):
 
     @staticmethod
     def reconstruct(H: Tensor, W: Tensor) -> Tensor:
+        """``F.convNd(H, W.flip(..), padding=T - 1)`` (nmf.py:776-779; NMF2D / NMF3D inherit this with two / three shift
+        axes) through the split-bf16 GEMM on the device.
+
+        Differentiable like the reference's convolution: with grad mode on and ``H`` or ``W`` requiring grad the result
+        carries a ``grad_fn`` whose backward is one ``nmfmu_conv_backward`` call (exact-fp32 MFMA, first order only).
+        Under ``torch.no_grad()`` -- ``fit()``, ``BetaMu.step`` -- nothing is recorded."""
         from .nmfd_engine import reconstruct as _recon
+        if torch.is_grad_enabled() and (H.requires_grad or W.requires_grad):
+            _require_device(H, 'reconstruct')
+            _require_device(W, 'reconstruct')
+            return _ConvReconstructFn.apply(H, W)
         return _recon(H, W)
 
     def _make_engine(self, V, beta, l1, l2, precision, group, allreduce=None):
