@@ -92,6 +92,15 @@ extern "C" {
                                   padded rank 256 with fp16 operands (the software-pipelined kernel: ONE image + transposing LDS
                                   reads) -- the fused apply / nmfmu_mu_apply no longer refresh the owner's p2 (64 of the 384 KiB a
                                   workgroup's epilogue moves).  Everywhere else it behaves as NMFMU_STAGE_DMA */
+#define NMFMU_STAGE_DMA_LDSTR 4 /* as NMFMU_STAGE_DMA, for the steps nmfmu_pp_lds_transpose_supported() names (the ping-pong kernel's
+                                   MU half-step at padded rank 128): the kernel fetches ONE panel image (p1) and builds the
+                                   transposed tile of the second GEMM in LDS from it (ds_read_b64_tr_b16 + ds_write_b64 in the
+                                   elementwise segments; same operands, same MFMA order: bit-identical results) -- half the
+                                   L2 -> LDS panel stream.  The caller promises that NOTHING reads the transposed images (p2_*) of
+                                   this step's factors: the step neither reads panel.p2_* nor refreshes owner.p2_* (fused apply and
+                                   nmfmu_mu_apply / nmfmu_trainer_apply alike; the buffers must still be allocated).  nmfmu_loss
+                                   treats it as NMFMU_STAGE_DMA; any other step answers NMFMU_ERR_UNSUPPORTED.  Appended under
+                                   ABI 9: no struct layout changes */
 #define NMFMU_STAGE_DMA_SPLIT 2 /* as NMFMU_STAGE_DMA, and panel.p1_* / panel.p2_* are images of DIFFERENT matrices (PLCA: the
                                    Z-scaled factor for the reconstruction, the unscaled one for the second GEMM).  Since ABI 6
                                    the single-plane four-wave kernels stage ONE panel image and gather the second GEMM's
@@ -159,6 +168,8 @@ int nmfmu_choose_nsplit(int owner_rows_pad, int panel_rows_pad, int block_rows, 
 #define NMFMU_KERNEL_SP 2    /* nmfmu::sp_kernel / sp2_kernel, four waves, software-pipelined across tiles, 128-row tiles
                                 (nmfmu_sp.h: beta == 1 at padded rank 256; nmfmu_sp2.h: beta != 1, 2 at padded rank 128; fp16) */
 int nmfmu_kernel_family(int r_pad, int precision, float beta);
+/* 1 when a half-step of this (padded rank, precision, beta) on 256-row tiles has the instance that NMFMU_STAGE_DMA_LDSTR selects */
+int nmfmu_pp_lds_transpose_supported(int r_pad, int precision, float beta);
 int nmfmu_choose_nsplit_for(int owner_rows_pad, int panel_rows_pad, int r_pad, int precision, float beta, int block_rows, int num_cu);
 /* tile height for ONE half-step of this shape (128 where the owner axis alone fills the chip, else nmfmu_block_rows) */
 int nmfmu_step_block_rows(int owner_rows_pad, int panel_rows_pad, int r_pad, int precision, float beta, int num_cu);

@@ -53,6 +53,10 @@ static bool pp_eligible(int r_pad, int precision, float beta) {
   return nmfmu_beta_kind(beta) == NMFMU_BETA_KL && r_pad <= 128 &&
          (precision == NMFMU_PREC_F16 || precision == NMFMU_PREC_BF16 || (NMFMU_PP_F16R && precision == NMFMU_PREC_F16R));
 }
+// ... and of those, the ones that have the instance which builds the transposed panel tile in LDS (NMFMU_STAGE_DMA_LDSTR)
+static bool pp_ldstr_eligible(int r_pad, int precision, float beta) {
+  return pp_eligible(r_pad, precision, beta) && pp_trl_available(r_pad, is_f16(precision) ? kOpF16 : kOpBf16, kModeMU);
+}
 // which half-steps the software-pipelined one-wave-per-SIMD kernel serves (nmfmu_sp.h): beta == 1, fp16 operands and target,
 // padded rank 256 -- the kernel of configs[4]'s shard
 static bool sp_eligible(int r_pad, int precision, float beta) {
@@ -84,8 +88,13 @@ int fused_dispatch(const nmfmu_step* st, int mode, float* loss_part, int M, int 
   if (!st->xp && (mode == kModeMU || mode == kModeXB)) return NMFMU_ERR_ARG;   // (the denominator-only pass and the loss may run without a target)
   if (st->owner.rows_pad % kRowPad || st->panel.rows_pad % kRowPad) return NMFMU_ERR_ARG;
   if (st->block_rows != 128 && st->block_rows != 256) return NMFMU_ERR_ARG;
-  if (st->stage != NMFMU_STAGE_DMA && st->stage != NMFMU_STAGE_DMA_SPLIT && st->stage != NMFMU_STAGE_DMA_NOP2)
+  if (st->stage != NMFMU_STAGE_DMA && st->stage != NMFMU_STAGE_DMA_SPLIT && st->stage != NMFMU_STAGE_DMA_NOP2 &&
+      st->stage != NMFMU_STAGE_DMA_LDSTR)
     return NMFMU_ERR_UNSUPPORTED;   // (register staging: no longer built)
+  // one panel image, the transposed tile built in LDS: the ping-pong kernel's MU half-step only (the loss reads p1 alone anyway)
+  const bool ldstr = st->stage == NMFMU_STAGE_DMA_LDSTR && mode != kModeLoss;
+  if (ldstr && (mode != kModeMU || st->block_rows != 256 || !pp_ldstr_eligible(st->r_pad, st->precision, st->beta)))
+    return NMFMU_ERR_UNSUPPORTED;
   // split panel (PLCA: p1 = the Z-scaled factor, p2 = the unscaled one): the instantiation that stages BOTH images
   if (st->stage == NMFMU_STAGE_DMA_SPLIT && mode == kModeMU && !(st->precision == NMFMU_PREC_BF16X3)) {
     if (nmfmu_beta_kind(st->beta) != NMFMU_BETA_KL || st->block_rows != 128) return NMFMU_ERR_UNSUPPORTED;
@@ -155,8 +164,9 @@ int fused_dispatch(const nmfmu_step* st, int mode, float* loss_part, int M, int 
 #ifdef NMFMU_DEBUG_HOOKS
     if (mode == kModeMU && g_pp_debug) a.debug = g_pp_debug;
 #endif
+    if (ldstr) a.o2_hi = nullptr;   // nobody reads the owner's transposed image: the fused apply skips it
     return launch_pp(st->r_pad, is_f16(st->precision) ? kOpF16 : kOpBf16, mode, a, grid, s, st->precision == NMFMU_PREC_F16R,
-                     /*riding loss*/ mode == kModeMU && loss_part != nullptr);
+                     /*riding loss*/ mode == kModeMU && loss_part != nullptr, ldstr);
   }
   if (mode == kModeMU && sp_eligible(st->r_pad, st->precision, st->beta)) {
     a.tiles_per_split = (a.tiles_per_split + 3) & ~3;   // its tile loop runs in groups of four (ring slot = tile & 3)
@@ -242,6 +252,8 @@ int nmfmu_kernel_family(int r_pad, int precision, float beta) {
   if (sp_eligible(r_pad, precision, beta) || sp2_eligible(r_pad, precision, beta)) return NMFMU_KERNEL_SP;
   return NMFMU_KERNEL_FUSED;
 }
+
+int nmfmu_pp_lds_transpose_supported(int r_pad, int precision, float beta) { return pp_ldstr_eligible(r_pad, precision, beta) ? 1 : 0; }
 
 int nmfmu_choose_nsplit_for(int owner_rows_pad, int panel_rows_pad, int r_pad, int precision, float beta, int block_rows, int num_cu) {
   if (owner_rows_pad <= 0 || panel_rows_pad <= 0 || (block_rows != 128 && block_rows != 256)) return NMFMU_ERR_ARG;
@@ -396,6 +408,10 @@ static int apply_common(const nmfmu_step* st, const float* num, const float* den
   a.status = st->status;
   if (!a.p1_hi || !a.p2_hi || !a.colsum || !a.colsum_part) return NMFMU_ERR_ARG;
   if (st->stage == NMFMU_STAGE_DMA_NOP2 && sp_eligible(st->r_pad, st->precision, st->beta)) a.p2_hi = a.p2_lo = nullptr;   // (see nmfmu.h)
+  if (st->stage == NMFMU_STAGE_DMA_LDSTR) {
+    if (st->block_rows != 256 || !pp_ldstr_eligible(st->r_pad, st->precision, st->beta)) return NMFMU_ERR_UNSUPPORTED;
+    a.p2_hi = a.p2_lo = nullptr;
+  }
   return launch_apply(st->r_pad, a, st->precision == NMFMU_PREC_BF16X3, /*pack_only=*/false, S(stream));
 }
 

@@ -8,6 +8,22 @@ bool pp_available(int r_pad, int opt, int mode) {
          (mode == kModeMU || mode == kModeLoss);
 }
 
+bool pp_trl_available(int r_pad, int opt, int mode) {
+  return r_pad == 128 && (opt == kOpBf16 || opt == kOpF16) && mode == kModeMU;
+}
+
+// the instances that build the P2 tiles in LDS (PPCfg::TRL): the MU half-step at padded rank 128, every form of it
+static int launch_pp_trl(int opt, const FusedArgs& a, int grid, hipStream_t s, bool xr, bool lacc) {
+  if (lacc) {
+    if (opt != kOpF16 || !a.loss_part) return -2;
+    return xr ? launch_pp_one<128, kOpF16, kModeMU, true, true, true>(a, grid, s) : launch_pp_one<128, kOpF16, kModeMU, false, true, true>(a, grid, s);
+  }
+  if (xr) return opt == kOpF16 ? launch_pp_one<128, kOpF16, kModeMU, true, false, true>(a, grid, s) : -2;
+  if (opt == kOpBf16) return launch_pp_one<128, kOpBf16, kModeMU, false, false, true>(a, grid, s);
+  if (opt == kOpF16) return launch_pp_one<128, kOpF16, kModeMU, false, false, true>(a, grid, s);
+  return -2;
+}
+
 template <int R_PAD>
 static int launch_pp_r(int opt, int mode, const FusedArgs& a, int grid, hipStream_t s, bool xr, bool lacc) {
   if (lacc) {   // riding loss (nmfmu_mu_step_with_loss): fp16 operands, MU half-step, either target width
@@ -26,7 +42,8 @@ static int launch_pp_r(int opt, int mode, const FusedArgs& a, int grid, hipStrea
   return -2;
 }
 
-int launch_pp(int r_pad, int opt, int mode, const FusedArgs& a, int grid, hipStream_t s, bool xr, bool lacc) {
+int launch_pp(int r_pad, int opt, int mode, const FusedArgs& a, int grid, hipStream_t s, bool xr, bool lacc, bool trl) {
+  if (trl) return pp_trl_available(r_pad, opt, mode) ? launch_pp_trl(opt, a, grid, s, xr, lacc) : -2;
   switch (r_pad) {
     case 32: return launch_pp_r<32>(opt, mode, a, grid, s, xr, lacc);
     case 64: return launch_pp_r<64>(opt, mode, a, grid, s, xr, lacc);

@@ -26,6 +26,9 @@
 //                          and wait for them with a COUNTED vmcnt at the end of their next M segment -- one barrier
 //                          before anybody (the operand prefetch of E(t+1)) reads them.  Waves 4-7 issue no panel
 //                          traffic: their segments are one barrier later, which would be one barrier too late.
+//                          The TRL instances (PPCfg::TRL, NMFMU_STAGE_DMA_LDSTR; MU half-step at padded rank 128) fetch P1 only
+//                          and build the P2 slot of tile t+1 from its P1 slot in LDS, in every wave's E(t): the transposing reads
+//                          that lost inside the M segment (below) cost nothing in the elementwise segment's shadow.
 //   X                    : global_load_dwordx4 ... nt straight into the lane that needs it (fragment order of
 //                          nmfmu_layout.h: a wave's share of a tile is one contiguous 4 KiB piece), two register
 //                          buffers, X(t+2) issued at the end of E(t) once the wave has consumed X(t).
@@ -71,7 +74,7 @@
 
 namespace nmfmu {
 
-template <int R_PAD, int OPT, int MODE, bool XR_ = false, bool LACC_ = false>
+template <int R_PAD, int OPT, int MODE, bool XR_ = false, bool LACC_ = false, bool TRL_ = false>
 struct PPCfg {
   static constexpr int BM = 256, WAVES = 8, THREADS = 512;
   static constexpr int KS = R_PAD / 16;      // k-steps of G1 (contraction over rank)
@@ -92,6 +95,16 @@ struct PPCfg {
   // Three VALU per element (v_log_f32, fused multiply-add, add) on the half-steps that carry it.
   static constexpr bool LACC = LACC_;
   static_assert(!LACC || (OPT == kOpF16 && MODE == kModeMU), "riding loss: fp16 operands, MU half-step");
+  // "transpose in LDS" (NMFMU_STAGE_DMA_LDSTR): the P2 ring slot of a tile is not fetched by LDS-DMA but built from the tile's
+  // P1 slot by the elementwise segments -- per wave and tile four ds_read_b64_tr_b16 (lane map: tools/ubench/tr_probe.hip; each
+  // lane receives four consecutive panel rows of one rank) and four ds_write_b64 into the [R_PAD][64] layout the M segment
+  // reads, at the addresses it reads today.  Wave w moves rank tile w & 3 of the panel rows 32 hl + 16 (w >> 2) + 0..15; all
+  // eight waves build P2(t+1) in their E(t) (P1(t+1) has landed one barrier earlier; the slot's last reader, G2(t-2), finished
+  // two barriers earlier; the first reader, A's M(t+2) -- or A's E(t+1) in the peeled last tile -- starts one barrier after
+  // the later half's E(t)), P2(0) in the prologue.  Half the L2 -> LDS panel stream, no P2 image in HBM at all: the kernel
+  // neither reads the panel's nor (fused apply) writes the owner's.  tests/test_pp_lds_transpose.py restates the lane map.
+  static constexpr bool TRL = TRL_;
+  static_assert(!TRL || (MODE == kModeMU && R_PAD == 128), "transpose in LDS: MU half-step at padded rank 128");
   static constexpr bool XM = (NMFMU_PP_DUP & (4 | 32)) ? false : (NMFMU_PP_XM < 0 ? XR : NMFMU_PP_XM != 0);   // X loads in the M segment
   static constexpr int P1_BASE = 0, P2_BASE = NSLOT * IMG;
   static constexpr int LDS_MAIN = 2 * NSLOT * IMG;
@@ -105,9 +118,9 @@ struct PPCfg {
   static_assert(NSTEP1 >= PF, "ring deeper than G1");
 };
 
-template <int R_PAD, int OPT, int MODE, bool XR = false, bool LACC = false>
+template <int R_PAD, int OPT, int MODE, bool XR = false, bool LACC = false, bool TRL = false>
 __global__ void __launch_bounds__(512, 2) pp_kernel(const FusedArgs a) {
-  using C = PPCfg<R_PAD, OPT, MODE, XR, LACC>;
+  using C = PPCfg<R_PAD, OPT, MODE, XR, LACC, TRL>;
   constexpr int NX = C::NX;
   constexpr int KS = C::KS, RT = C::RT, ROWB = C::ROWB, IMG = C::IMG, PF = C::PF;
   constexpr int NSTEP1 = C::NSTEP1, NSTEP2 = C::NSTEP2;
@@ -256,7 +269,7 @@ __global__ void __launch_bounds__(512, 2) pp_kernel(const FusedArgs a) {
     auto next_off = [&](unsigned off) { return off == (unsigned)(C::NSLOT - 1) * IMG ? 0u : off + IMG; };
     auto issue_panel = [&](int t) {   // called in E(t) by waves 0-3: P1(t + LEAD), P2(t + LEAD - 1)
       dma_img(p1src + (size_t)clampt(t + C::LEAD) * IMG, C::P1_BASE + p1_issue_off);
-      if constexpr (!C::LOSS) dma_img(p2src + (size_t)clampt(t + C::LEAD - 1) * IMG, C::P2_BASE + p2_issue_off);
+      if constexpr (!C::LOSS && !C::TRL) dma_img(p2src + (size_t)clampt(t + C::LEAD - 1) * IMG, C::P2_BASE + p2_issue_off);
     };
     // this wave's four 1-KiB pieces of X(t), one 16-byte chunk per lane each, loaded by asm so that hipcc neither
     // counts nor waits for them; wait_x() is the counted wait that makes a buffer readable.  Non-temporal: X is read once
@@ -372,11 +385,44 @@ __global__ void __launch_bounds__(512, 2) pp_kernel(const FusedArgs a) {
 #pragma unroll
       for (int m2 = 0; m2 < 2; ++m2) sb[tt][m2] = b_base[tt][m2] + C::P2_BASE + BACK;
     int rd1 = 0, rd2 = BACK;   // current slot offsets of sa / sb (uniform)
+    // transpose in LDS: per-lane source (P1 slot) and destination (P2 slot) of the wave's share, pair p = 0..3 = panel rows
+    // 4 p .. 4 p + 3 of the wave's sixteen: source (tr_src ^ 16 p) + 1024 p, destination (tr_dst ^ 16 (p >> 1)) + 8 (p & 1).
+    // Both follow the P1 slot of the tile sa points to (tile t+1 in E(t), tile 0 in the prologue).
+    int tr_src = 0, tr_dst = 0;
+    if constexpr (C::TRL) {
+      const int rt = wave & 3, tt = wave >> 2, grp = lane >> 4, s16 = lane & 15, i4 = s16 >> 2;
+      const int cslot = 2 * (grp & 1) + ((s16 & 3) >> 1);
+      tr_src = C::P1_BASE + (32 * (grp >> 1) + 16 * tt + i4) * ROWB + (((((rt ^ i4) << 2) | cslot) << 4) + 8 * (s16 & 1));
+      tr_dst = C::P2_BASE + (32 * rt + j) * 128 + (((4 * hl + 2 * tt) ^ ((j >> 1) & 7)) << 4);
+    }
+    using u32x2 = __attribute__((ext_vector_type(2))) uint32_t;
+    u32x2 trv[4];
+    auto tr_rd = [&](u32x2& dst, int addr, auto offc) {
+      asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(decltype(offc)::value));
+    };
+    auto tr_wr = [&](const u32x2& v, int addr, auto offc) {
+      asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(addr), "v"(v), "n"(decltype(offc)::value) : "memory");
+    };
+    auto transpose_read = [&]() {    // four rows x sixteen ranks per sixteen lanes, delivered rank-major
+      tr_rd(trv[0], tr_src, std::integral_constant<int, 0>{});
+      tr_rd(trv[1], tr_src ^ 16, std::integral_constant<int, 4 * ROWB>{});
+      tr_rd(trv[2], tr_src ^ 32, std::integral_constant<int, 8 * ROWB>{});
+      tr_rd(trv[3], tr_src ^ 48, std::integral_constant<int, 12 * ROWB>{});
+    };
+    auto transpose_write = [&]() {   // own wait: nothing of this wave's is outstanding in LDS afterwards but the four writes
+      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(trv[0]), "+v"(trv[1]), "+v"(trv[2]), "+v"(trv[3])::"memory");
+      tr_wr(trv[0], tr_dst, std::integral_constant<int, 0>{});
+      tr_wr(trv[1], tr_dst, std::integral_constant<int, 8>{});
+      tr_wr(trv[2], tr_dst ^ 16, std::integral_constant<int, 0>{});
+      tr_wr(trv[3], tr_dst ^ 16, std::integral_constant<int, 8>{});
+    };
+    auto transpose_done = [&]() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); };   // ... in front of the barrier
     auto advance_slots = [&]() {   // sa -> P1 slot of the next tile, sb -> P2 slot of the tile before it
       const int d1 = rd1 == BACK ? -BACK : IMG;
       const int d2 = rd2 == BACK ? -BACK : IMG;
       rd1 += d1, rd2 += d2;
       sa[0] += d1, sa[1] += d1;
+      if constexpr (C::TRL) tr_src += d1, tr_dst += d1;
       if constexpr (!C::LOSS) {
 #pragma unroll
         for (int tt = 0; tt < 2; ++tt)
@@ -504,15 +550,25 @@ __global__ void __launch_bounds__(512, 2) pp_kernel(const FusedArgs a) {
       constexpr bool next_has_g1 = decltype(nextc)::value;
       constexpr bool tail = decltype(tailc)::value;
       advance_slots();
+      // transpose in LDS: P2(t+1) from P1(t+1), ahead of the operand pre-reads; the writes follow the first half of the ratios
+      // (the reads have long landed by then), their completion is awaited at the end of the segment
+      constexpr bool trl = C::TRL && next_has_g1;
+      if constexpr (trl) transpose_read();
       if constexpr (next_has_g1) prefetch(std::true_type{});
       else if constexpr (!C::LOSS) prefetch(std::false_type{});
       if constexpr (!tail) {
         if (!half) issue_panel(t);
-      } else if constexpr (next_has_g1 && !C::LOSS) {   // tile nt-2: only P2(nt-1) is still needed
+      } else if constexpr (next_has_g1 && !C::LOSS && !C::TRL) {   // tile nt-2: only P2(nt-1) is still needed
         if (!half) dma_img(p2src + (size_t)(t + 1) * IMG, C::P2_BASE + p2_issue_off);
       }
 #pragma unroll
       for (int tt = 0; tt < 2; ++tt) {
+        if constexpr (trl) {
+          if (tt == 1) {
+            __builtin_amdgcn_sched_barrier(0);   // (the ratio statements are not volatile: keep the wait behind the first sixteen)
+            transpose_write();
+          }
+        }
         if constexpr (C::LOSS) {
 #pragma unroll
           for (int d = 0; d < 8; ++d) {
@@ -661,13 +717,14 @@ __global__ void __launch_bounds__(512, 2) pp_kernel(const FusedArgs a) {
       p2_issue_off = next_off(p2_issue_off);
       __builtin_amdgcn_sched_barrier(0);   // this wave's reads of X(t) are complete (their values were consumed)
       if constexpr (!tail && !C::XM) load_x(t + 2, x);   // ... before its register buffer is refilled (XM: in the next M segment)
+      if constexpr (trl) transpose_done();
     };
 
     // ---- prologue: P1(0), P1(1), P2(0), X(0), X(1); everything landed before the first barrier
     if (!half) {
 #pragma unroll
       for (int i = 0; i < C::LEAD; ++i) dma_img(p1src + (size_t)clampt(i) * IMG, C::P1_BASE + i * IMG);
-      if constexpr (!C::LOSS) {
+      if constexpr (!C::LOSS && !C::TRL) {
 #pragma unroll
         for (int i = 0; i < C::LEAD - 1; ++i) dma_img(p2src + (size_t)clampt(i) * IMG, C::P2_BASE + i * IMG);
       }
@@ -684,6 +741,11 @@ __global__ void __launch_bounds__(512, 2) pp_kernel(const FusedArgs a) {
 #endif
     scale_owner();
     barrier();
+    if constexpr (C::TRL) {   // P2(0) from P1(0): complete two barriers before its first reader, A's M(1)
+      transpose_read();
+      transpose_write();
+      transpose_done();
+    }
     prefetch(std::true_type{});
     if (half) barrier();                       // waves 4-7 run one segment behind
     matrix_segment(std::true_type{}, std::false_type{}, std::false_type{}, no_fill);
@@ -878,19 +940,22 @@ __global__ void __launch_bounds__(512, 2) pp_kernel(const FusedArgs a) {
       if constexpr (OPT == kOpF16) {
         if (a.status && __any(clamped) && lane_e == 0) atomicOr(a.status, 1u);
       }
-      __syncthreads();
       // transposed image from the updated tile: 8 consecutive owner rows of one rank = one sixteen-byte slot
+      // (a.o2_hi == nullptr -- NMFMU_STAGE_DMA_LDSTR: nobody reads the owner's transposed image; the pass and its barrier go)
+      if (a.o2_hi) {
+        __syncthreads();
 #pragma unroll
-      for (int ii = 0; ii < R_PAD / 64 + (R_PAD < 64 ? 1 : 0); ++ii) {
-        const int r = ii * 64 + lane_e;
-        if (r < R_PAD) {
+        for (int ii = 0; ii < R_PAD / 64 + (R_PAD < 64 ? 1 : 0); ++ii) {
+          const int r = ii * 64 + lane_e;
+          if (r < R_PAD) {
 #pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            const float* src = tile + (g * 8) * LDT + r;
-            u32x4 hi;
+            for (int g = 0; g < 4; ++g) {
+              const float* src = tile + (g * 8) * LDT + r;
+              u32x4 hi;
 #pragma unroll
-            for (int qq = 0; qq < 4; ++qq) hi[qq] = pack_op<OPT>(src[(2 * qq) * LDT], src[(2 * qq + 1) * LDT]);
-            *reinterpret_cast<u32x4*>(reinterpret_cast<char*>(a.o2_hi) + p2_offset(mrow0 + g * 8, r, R_PAD)) = hi;
+              for (int qq = 0; qq < 4; ++qq) hi[qq] = pack_op<OPT>(src[(2 * qq) * LDT], src[(2 * qq + 1) * LDT]);
+              *reinterpret_cast<u32x4*>(reinterpret_cast<char*>(a.o2_hi) + p2_offset(mrow0 + g * 8, r, R_PAD)) = hi;
+            }
           }
         }
       }
@@ -930,14 +995,17 @@ __global__ void __launch_bounds__(512, 2) pp_kernel(const FusedArgs a) {
   }
 }
 
-template <int R_PAD, int OPT, int MODE, bool XR = false, bool LACC = false>
+template <int R_PAD, int OPT, int MODE, bool XR = false, bool LACC = false, bool TRL = false>
 int launch_pp_one(const FusedArgs& a, int grid, hipStream_t s) {
-  using C = PPCfg<R_PAD, OPT, MODE, XR, LACC>;
-  return launch_with_dynamic_lds<pp_kernel<R_PAD, OPT, MODE, XR, LACC>, C::THREADS, C::LDS_BYTES>(dim3(grid), s, a);
+  using C = PPCfg<R_PAD, OPT, MODE, XR, LACC, TRL>;
+  return launch_with_dynamic_lds<pp_kernel<R_PAD, OPT, MODE, XR, LACC, TRL>, C::THREADS, C::LDS_BYTES>(dim3(grid), s, a);
 }
 
 // Host-side launcher (nmfmu_inst_pp.hip).  opt = OperandType, mode = kModeMU | kModeLoss.
-int launch_pp(int r_pad, int opt, int mode, const FusedArgs& a, int grid, hipStream_t s, bool xr = false, bool lacc = false);
+// trl: the instance that builds the P2 tiles in LDS (PPCfg::TRL; kModeMU at padded rank 128, else -2)
+int launch_pp(int r_pad, int opt, int mode, const FusedArgs& a, int grid, hipStream_t s, bool xr = false, bool lacc = false,
+              bool trl = false);
 bool pp_available(int r_pad, int opt, int mode);
+bool pp_trl_available(int r_pad, int opt, int mode);
 
 }  // namespace nmfmu

@@ -21,6 +21,8 @@ ERR_ALLOC = -4
 PREC_BF16, PREC_BF16X3, PREC_F16, PREC_F16X, PREC_F16R = 0, 1, 2, 3, 4
 STAGE_REG, STAGE_DMA, STAGE_DMA_SPLIT = 0, 1, 2
 STAGE_DMA_NOP2 = 3          # as STAGE_DMA; nothing reads the factors' transposed images (include/nmfmu.h)
+STAGE_DMA_LDSTR = 4         # ping-pong MU half-step at padded rank 128: one panel image, the transposed tile built in LDS;
+                            # nothing reads or refreshes the factors' transposed images (include/nmfmu.h)
 BETA_KL, BETA_EUC, BETA_IS, BETA_GEN = 0, 1, 2, 3
 KERNEL_FUSED, KERNEL_PP, KERNEL_SP = 0, 1, 2
 
@@ -75,6 +77,7 @@ SIGNATURES = {
     'nmfmu_step_block_rows': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int]),
     'nmfmu_choose_nsplit': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     'nmfmu_kernel_family': (C.c_int, [C.c_int, C.c_int, C.c_float]),
+    'nmfmu_pp_lds_transpose_supported': (C.c_int, [C.c_int, C.c_int, C.c_float]),
     'nmfmu_choose_nsplit_for': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int]),
     'nmfmu_xp_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     'nmfmu_image_bytes': (C.c_size_t, [C.c_int, C.c_int]),

@@ -72,6 +72,9 @@ class HipBackend:
     def kernel_family(self, r_pad: int, precision: int, beta: float) -> int:
         return self.lib.nmfmu_kernel_family(r_pad, precision, beta)
 
+    def pp_lds_transpose_supported(self, r_pad: int, precision: int, beta: float) -> bool:
+        return bool(self.lib.nmfmu_pp_lds_transpose_supported(r_pad, precision, beta))
+
     @staticmethod
     def stream() -> int:
         return torch.cuda.current_stream().cuda_stream
@@ -556,6 +559,14 @@ class DenseMU(AsyncLossMixin):
                     and self.r_pad == 256 and self.be.kernel_family(self.r_pad, self.precision, float(beta)) == _capi.KERNEL_SP
                     and os.environ.get('TORCHNMF_AMD_NO_P2', '1') != '0')
             stage = _capi.STAGE_DMA_NOP2 if nop2 else _capi.STAGE_DMA
+            # beta == 1 at padded rank 128, unsharded, both factors updated: BOTH half-steps run the ping-pong MU kernel, whose
+            # NMFMU_STAGE_DMA_LDSTR instance fetches one panel image and builds the transposed tile in LDS -- nothing reads the
+            # factors' transposed images, nobody refreshes them.  (Sharded engines keep the two-image path; so does a forced
+            # 128-row tile, which runs the four-wave kernel.)
+            if (group is None and update_W and block_rows in (None, 256) and hasattr(self.be, 'pp_lds_transpose_supported')
+                    and self.be.pp_lds_transpose_supported(self.r_pad, self.precision, float(beta))
+                    and self.be.block_rows(self.r_pad, self.precision, float(beta)) == 256):
+                stage = _capi.STAGE_DMA_LDSTR
         # beta == 2 without the reconstruction (nmf.py:61-63 has no eps inside its grad_outputs): numerator = one streaming
         # GEMM over X, denominator through the panel's rank x rank Gram matrix -- a third of the MFMA work, HBM-bound.
         # fit()'s engines only (allow_gram): BetaMu reads numerator AND denominator slabs (p.grad = pos - neg).
