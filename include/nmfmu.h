@@ -53,7 +53,9 @@ extern "C" {
                                   NMFMU_PREC_F16R (3-byte target);
                                   still 9, purely additive: nmfmu_reconstruct_backward / nmfmu_reconstruct_backward_ws /
                                   nmfmu_beta_div_grad (torch.autograd through NMF.forward and the divergences);
-                                  nmfmu_conv_backward / nmfmu_conv_backward_ws (the same through NMFD / NMF2D / NMF3D.forward) */
+                                  nmfmu_conv_backward / nmfmu_conv_backward_ws (the same through NMFD / NMF2D / NMF3D.forward);
+                                  nmfmu_hoyer_project / nmfmu_hoyer_project_ws (batched Hoyer projection behind sparse_fit and
+                                  trainer.SparsityProj) */
 
 #define NMFMU_OK 0
 #define NMFMU_ERR_UNSUPPORTED (-2) /* rank / precision / beta combination not built */
@@ -377,6 +379,29 @@ int64_t nmfmu_conv_backward_ws(int batch, int channels, int rank, int ndim, cons
                                int want_w, int* splits);
 int nmfmu_conv_backward(const float* g, const float* w, const float* h, int batch, int channels, int rank, int ndim,
                         const int32_t* lh, const int32_t* taps, float* grad_h, float* grad_w, float* ws, void* stream);
+
+/* nmfmu_hoyer_project: Hoyer's projection onto {v >= 0, sum v = k1, sum v^2 = k2} (Hoyer 2004, section 3.3; the reference's
+ * nmf.py:21-49) of every slice of a factor, in place, in ONE call with no host round trip.  x is a contiguous fp32 tensor seen
+ * as [outer][J][inner]; slice j is every element with index j on the middle axis (n = outer * inner elements): dim = 1 of
+ * W (C, R), H (N, R), W (C, R, *T), H (B, R, *L), or any dim of any contiguous tensor.  k1[j] / k2[j] are slice j's L1 and squared
+ * L2 targets, device arrays of J floats.  Per slice:
+ *   v = s + (k1 - sum s) / n;  zeroed = {}
+ *   repeat:  m = k1 / (n - |zeroed|);  w_i = v_i - m for i not zeroed, w_i = v_i for i zeroed (sic, as the reference)
+ *            alpha = (-b + sqrt(max(b^2 - 4 a c, 0))) / (2 a),  a = w.w, b = 2 w.v, c = v.v - k2;  v += alpha w
+ *            no v_i < 0: stop (a NaN compares false and ends the loop too)
+ *            zeroed |= {v_i < 0};  v = max(v, 0);  v += (k1 - sum v) / (n - |zeroed|) on EVERY coordinate (sic);  v = max(v, 0)
+ * One workgroup of 256 threads owns a slice for its whole loop (grid = J workgroups; no atomics, no spin-waits).  Elementwise
+ * arithmetic is fp32; the block-wide sums and the scalars derived from them are fp64.  The loop is capped at n passes:
+ * status[j] (J ints on the device, may be NULL) = the number of passes made, negated when the cap ended the loop.  Degenerate
+ * slices (n = 1, all zero, k2 = 0) return NaN like the reference.
+ * Residency: n <= lds_max_elems (<= 0 or anything above the built maximum of 40896 means that maximum) keeps the slice in
+ * LDS between its one strided read and its one strided write; a longer slice is streamed from a slice-major copy in `ws`,
+ * built and written back by a tiled transpose (a tensor with outer == 1 or J == 1 is slice-major already and streamed in place).
+ * nmfmu_hoyer_project_ws (host only) returns the BYTES `ws` must hold for these arguments (0: ws may be NULL) or an error
+ * code.  n >= 2^31 or J < 1: NMFMU_ERR_UNSUPPORTED.  Nothing is allocated inside the library. */
+int64_t nmfmu_hoyer_project_ws(int64_t outer, int J, int64_t inner, int lds_max_elems);
+int nmfmu_hoyer_project(float* x, int64_t outer, int J, int64_t inner, const float* k1, const float* k2, int lds_max_elems,
+                        void* ws, int* status, void* stream);
 
 /* ---- convolutive NMF (NMFD, nmf.py:700-779) --------------------------------------------------------------------
  * NMFD is dense NMF on unfolded operands with effective rank R*T: with W (C,R,T) viewed as Wm (C x R*T) and

@@ -127,6 +127,9 @@ SIGNATURES = {
                                       C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p]),
     'nmfmu_beta_div_grad': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'nmfmu_hoyer_project_ws': (C.c_int64, [C.c_int64, C.c_int, C.c_int64, C.c_int]),
+    'nmfmu_hoyer_project': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                      C.c_void_p, C.c_void_p]),
     'nmfmu_gemm': (C.c_int, [C.POINTER(GemmDesc), C.c_int, C.c_void_p]),
     'nmfmu_gemm_window_staged': (C.c_int, [C.POINTER(GemmDesc), C.c_int]),
     'nmfmu_pack2d': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_int64,

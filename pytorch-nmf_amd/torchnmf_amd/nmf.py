@@ -13,7 +13,9 @@ on ``forward`` / ``fit``).
 the same engines.  ``NMF.forward`` / ``NMF.reconstruct`` are differentiable (``torch.autograd`` through an exact-fp32
 MFMA backward, ``nmfmu_reconstruct_backward``): ``beta_div(m(), V, beta).backward()`` and any ``torch.optim`` optimizer
 work as in the reference.  The convolutive ``forward`` (``NMFD`` / ``NMF2D`` / ``NMF3D``) is differentiable the same way
-(``nmfmu_conv_backward``).  Out of scope: ``sparse_fit`` (Hoyer-projected gradient).
+(``nmfmu_conv_backward``).  ``sparse_fit`` (Hoyer's sparseness-constrained fitting, nmf.py:411-599) runs on those backward
+kernels, the MU engines and one batched projection kernel (``hoyer.hoyer_project`` / ``nmfmu_hoyer_project``) for dense targets
+on all four model classes; sparse-COO targets of ``sparse_fit`` are not implemented.
 """
 from __future__ import annotations
 
@@ -223,9 +225,155 @@ class BaseComponent(nn.Module):
     def _make_engine(self, V, beta, l1, l2, precision, group, allreduce=None):
         raise NotImplementedError
 
-    def sparse_fit(self, *args, **kwargs):
-        raise NotImplementedError('sparse_fit (Hoyer-projected gradient, nmf.py:411-599) is outside the MU hot path '
-                                  'this engine implements')
+    def _projected_half_step(self, p, recon, V, beta: float, l1: float, stepsize: float) -> float:
+        """One sparseness-constrained half-step on the factor ``p`` (nmf.py:494-520 / 545-572): the gradient of
+        ``beta_div(recon(p), V, beta)`` through the autograd kernels, then up to 10 tries of gradient step, projection of
+        every slice along dim 1 (ONE launch; k1 = l1 * norm, k2 = norm^2, formed on the device) and loss, accepting the
+        first try whose loss did not grow (the one host sync of a try); the step size halves per rejection and grows by
+        1.2 at the end.  The last candidate is stored whether accepted or not, as in the reference."""
+        from .hoyer import hoyer_project, slice_norms
+        from .metrics import beta_div
+        p.grad = None
+        with torch.enable_grad():
+            loss = beta_div(recon(p), V, beta)
+            loss.backward()
+        with torch.no_grad():
+            grad = p.grad
+            for _ in range(10):
+                new = p - stepsize * grad
+                norms = slice_norms(new, 1)
+                hoyer_project(new, l1 * norms, norms * norms, 1, out=new)
+                new_loss = beta_div(recon(new), V, beta)
+                if new_loss <= loss:
+                    break
+                stepsize *= 0.5
+            stepsize *= 1.2
+            p.copy_(new)
+        return stepsize
+
+    def sparse_fit(self, V: Tensor, beta: float = 2, max_iter: int = 200, verbose: bool = False,
+                   sW: Optional[float] = None, sH: Optional[float] = None) -> int:
+        """Minimise the beta-divergence under Hoyer's sparseness constraints (Hoyer 2004; reference nmf.py:411-599).
+
+        ``sW`` / ``sH`` in (0, 1) fix the sparseness of every ``W[:, r]`` / ``H[:, r]``; ``None`` leaves that factor
+        unconstrained.  The constrained factors are first projected to unit L2 norm at the target sparseness.  Then, every
+        iteration: a half-step on W, a half-step on H, ``H`` renormalised to unit L2 norm per component (W rescaled to
+        compensate).  An unconstrained half-step is the multiplicative update of ``fit`` (l1 = l2 = 0) on the MU engine in
+        its fp32-grade split-bf16 mode ('bf16x3', fixed: ``fit``'s ``precision`` choice and TORCHNMF_AMD_PRECISION do not apply
+        here, the line search compares losses of neighbouring points); a constrained one is a projected gradient step with a halving line search
+        (``_projected_half_step``) whose projection is one launch of the batched HIP kernel (``hoyer.hoyer_project``).
+        Returns the number of iterations (always ``max_iter``: there is no stopping rule); with ``verbose`` a progress bar
+        shows ``sqrt(2 * loss)`` every 10th iteration.
+
+        Dense targets on all four model classes.  Sparse-COO targets raise ``NotImplementedError``: they are deliberately
+        left out (the reference's sparse loss path is a second implementation of every step above).  A module in another
+        float dtype is fitted on fp32 working copies and keeps its dtype, as in ``fit``.
+
+        There is no CPU path: a module or target that is not on the ROCm device raises ``NotImplementedError`` ("sparse_fit
+        has no CPU path") before the library is loaded -- the one place where the missing CPU fallback is not an
+        ``NmfmuError`` (this entry point answered ``NotImplementedError`` before it existed, and callers rely on it)."""
+        W, H = self.W, self.H
+        assert W is not None and H is not None
+        for t in (V, W, H):
+            if t.device.type != 'cuda':
+                raise NotImplementedError(f'sparse_fit has no CPU path: tensors live on {t.device}; torchnmf_amd computes '
+                                          f'on an MI355X only -- move the module and its target with .cuda()')
+        if V.is_sparse:
+            raise NotImplementedError('sparse_fit: sparse-COO targets are not implemented (dense targets only); use '
+                                      'V.to_dense(), or NMF.fit for the multiplicative update on a sparse target')
+        if W.dtype != torch.float32 or H.dtype != torch.float32:
+            if not (W.dtype.is_floating_point and H.dtype.is_floating_point):
+                raise NotImplementedError(f'factors must be floating point; got W {W.dtype}, H {H.dtype}')
+            keep = (W.data, H.data)
+            W.grad = H.grad = None
+            W.data, H.data = W.data.float().contiguous(), H.data.float().contiguous()
+            try:
+                return self.sparse_fit(V, beta, max_iter, verbose, sW, sH)
+            finally:
+                w32, h32 = W.data, H.data
+                W.grad = H.grad = None
+                W.data, H.data = keep
+                W.data.copy_(w32)
+                H.data.copy_(h32)
+        from .hoyer import hoyer_project, slice_norms
+        from .metrics import beta_div
+        beta = float(beta)
+        V = V.detach()
+        if V.dtype != torch.float32:
+            V = V.float()
+        V = V.contiguous()
+        v_min = float(V.min()) if V.numel() else 0.0
+        assert v_min >= 0, "Target should be non-negative."          # (NaN fails too, like torch.all(V >= 0))
+        if v_min == 0 and beta <= 0:
+            raise ValueError("When beta <= 0 and V contains zeros, the training process may diverge. "
+                             "Please add small values to V, or use a positive beta value.")
+        for q in (W, H):
+            if not q.data.is_contiguous():
+                q.data = q.data.contiguous()
+
+        def unit_l1(q, s):         # L1 norm of a unit-L2 slice with sparseness s (nmf.py:459-472)
+            n = q[:, 0].numel()
+            return n ** 0.5 * (1 - s) + s
+        l1_w = unit_l1(W, sW) if sW is not None and W.requires_grad else None
+        l1_h = unit_l1(H, sH) if sH is not None and H.requires_grad else None
+        if l1_w is not None:
+            hoyer_project(W.data, l1_w, 1.0, 1, out=W.data)
+        if l1_h is not None:
+            hoyer_project(H.data, l1_h, 1.0, 1, out=H.data)
+
+        mu_w, mu_h = W.requires_grad and l1_w is None, H.requires_grad and l1_h is None
+        eng = None
+        if mu_w or mu_h:
+            # the fp32-grade mode of the MU engine ('bf16x3'; NMF above rank 128 runs it on the GEMM engine): the line search
+            # compares losses of neighbouring points, a single-plane operand mode is not its grade
+            with torch.no_grad():
+                eng = self._make_engine(V, beta, 0.0, 0.0, 'bf16x3', None)
+        stale = False                  # W / H changed behind the engine's back: its operand images must be rebuilt
+
+        def mu_step(which):
+            nonlocal stale
+            with torch.no_grad():
+                if stale:
+                    eng.refresh_images()
+                    stale = False
+                eng.w_step() if which == 'W' else eng.h_step()
+
+        def renorm_h():                # _renorm(W, H, 'H'), nmf.py:139-158
+            with torch.no_grad():
+                norms = slice_norms(H.data, 1)
+                H.data /= norms.view((1, -1) + (1,) * (H.dim() - 2))
+                W.data *= norms.view((1, -1) + (1,) * (W.dim() - 2))
+
+        step_w = step_h = 1.0
+        pbar = None
+        if verbose:
+            from tqdm import tqdm
+            pbar = tqdm(total=max_iter)
+        n_iter = -1
+        try:
+            for n_iter in range(max_iter):
+                if W.requires_grad:
+                    if l1_w is None:
+                        mu_step('W')
+                    else:
+                        step_w = self._projected_half_step(W, lambda w: self.reconstruct(H.detach(), w), V, beta, l1_w, step_w)
+                        stale = True
+                if H.requires_grad:
+                    if l1_h is None:
+                        mu_step('H')
+                    else:
+                        step_h = self._projected_half_step(H, lambda h: self.reconstruct(h, W.detach()), V, beta, l1_h, step_h)
+                    renorm_h()
+                    stale = True
+                if pbar is not None and n_iter % 10 == 9:
+                    with torch.no_grad():
+                        loss = _sqrt2(float(beta_div(self.reconstruct(H, W), V, beta)))
+                    pbar.set_postfix(loss=loss)
+                    pbar.update(10)
+        finally:
+            if pbar is not None:
+                pbar.close()
+        return n_iter + 1
 
     @torch.no_grad()
     def fit(self, V: Tensor, beta: float = 1, tol: float = 1e-4, max_iter: int = 200, verbose: bool = False,

@@ -666,6 +666,11 @@ class WideRankMU:
     def target_flags(self):
         return self.eng.target_flags()
 
+    def refresh_images(self):
+        """After external edits of W / H (sparse_fit): the transposed working copy of H, then the engine's images."""
+        self.Ht[0].copy_(self.H_user.t())
+        self.eng.refresh_images()
+
     def w_step(self):
         self.eng.w_step()
 

@@ -37,13 +37,70 @@ __all__ = ['BetaMu', 'SparsityProj']
 
 
 class SparsityProj(Optimizer):
-    """Placeholder for the reference's Hoyer-projected gradient optimizer (torchnmf/trainer.py:124-226).  It is a
-    different algorithm (serial projection loop) outside the MU hot path this engine implements (SURVEY.md section 2);
-    importing the name works, constructing it says so."""
+    """Hoyer's sparseness-constrained projected gradient step (same arguments, checks and group state as the reference,
+    trainer.py:124-190).
 
-    def __init__(self, *args, **kwargs):
-        raise NotImplementedError('trainer.SparsityProj (Hoyer-projected gradient, trainer.py:124-226) is outside the MU '
-                                  'hot path torchnmf_amd implements; use the reference package for sparse_fit')
+    ``step(closure)`` evaluates ``closure()`` and back-propagates it (any differentiable device graph: the package's own
+    ``forward`` / ``beta_div`` run their HIP backward kernels), then tries up to ``max_iter`` times: gradient step of size
+    ``lr``, projection of every slice of every parameter along ``dim`` onto the L1 / L2 pair that gives it the sparseness
+    ``sparsity`` at its current L2 norm, re-evaluation of the closure; a try is accepted when the loss did not grow, else the
+    step is undone and ``lr`` halved.  After the tries ``lr *= 1.2``.  The projection of ALL slices of a parameter is ONE
+    launch of the batched HIP kernel (``hoyer.hoyer_project``) whose targets are device tensors: the only host sync of a try
+    is the loss comparison.  As in the reference (trainer.py:153-185) only the first evaluation runs with grad mode on; the
+    re-evaluations of the line search run under ``torch.no_grad()``, so the closure must not call ``backward()`` itself.
+
+    float32 parameters on the ROCm device only: other dtypes raise ``NotImplementedError`` (as ``BetaMu`` does), CPU
+    parameters ``NmfmuError``.
+
+        trainer = SparsityProj([m.W], sparsity=0.3)
+        def closure():
+            trainer.zero_grad()
+            return beta_div(m(), V, 2)
+        trainer.step(closure)
+    """
+
+    def __init__(self, params, sparsity, dim=1, max_iter=10):
+        if not 0.0 < sparsity < 1.:
+            raise ValueError("Invalid sparsity value: {}".format(sparsity))
+        defaults = dict(sparsity=sparsity, lr=1, dim=dim, max_iter=max_iter)
+        super().__init__(params, defaults)
+
+    @torch.no_grad()
+    def step(self, closure):
+        """One projected gradient step per parameter group (trainer.py:153-190); returns the last loss evaluated."""
+        from . import _capi
+        from .hoyer import hoyer_project, slice_norms
+        for group in self.param_groups:
+            for p in group['params']:
+                if p.device.type != 'cuda':
+                    raise _capi.NmfmuError(f'SparsityProj: a parameter lives on {p.device}; torchnmf_amd computes on an '
+                                           f'MI355X only (there is no CPU fallback)')
+                if p.dtype != torch.float32:
+                    raise NotImplementedError(f'SparsityProj needs float32 parameters (the projection kernel works on '
+                                              f'their storage in place); got {p.dtype}')
+        loss = None
+        for group in self.param_groups:
+            sparsity, lr, dim, max_iter = group['sparsity'], group['lr'], group['dim'], group['max_iter']
+            with torch.enable_grad():
+                init_loss = closure()
+                init_loss.backward()
+            params = [(p, p.grad.clone()) for p in group['params'] if p.grad is not None]
+            for _ in range(max_iter):
+                for p, g in params:
+                    norms = slice_norms(p, dim)
+                    p.add_(g, alpha=-lr)
+                    n = p.numel() // p.shape[dim]
+                    l1 = n ** 0.5 * (1 - sparsity) + sparsity
+                    hoyer_project(p, l1 * norms, norms * norms, dim, out=p)
+                loss = closure()
+                if loss <= init_loss:          # the one host sync of a try
+                    break
+                for p, g in params:
+                    p.add_(g, alpha=lr)
+                lr *= 0.5
+            lr *= 1.2
+            group['lr'] = lr
+        return loss
 
 
 class _ConvBinding:
