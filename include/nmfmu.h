@@ -55,7 +55,10 @@ extern "C" {
                                   nmfmu_beta_div_grad (torch.autograd through NMF.forward and the divergences);
                                   nmfmu_conv_backward / nmfmu_conv_backward_ws (the same through NMFD / NMF2D / NMF3D.forward);
                                   nmfmu_hoyer_project / nmfmu_hoyer_project_ws (batched Hoyer projection behind sparse_fit and
-                                  trainer.SparsityProj) */
+                                  trainer.SparsityProj);
+                                  nmfmu_plca_backward / nmfmu_plca_backward_ws / nmfmu_conv_plca_backward /
+                                  nmfmu_conv_plca_backward_ws (torch.autograd through PLCA / SIPLCA / SIPLCA2 / SIPLCA3.forward:
+                                  the two products above, finished with the latent vector Z) */
 
 #define NMFMU_OK 0
 #define NMFMU_ERR_UNSUPPORTED (-2) /* rank / precision / beta combination not built */
@@ -379,6 +382,50 @@ int64_t nmfmu_conv_backward_ws(int batch, int channels, int rank, int ndim, cons
                                int want_w, int* splits);
 int nmfmu_conv_backward(const float* g, const float* w, const float* h, int batch, int channels, int rank, int ndim,
                         const int32_t* lh, const int32_t* taps, float* grad_h, float* grad_w, float* ws, void* stream);
+
+/* nmfmu_plca_backward / nmfmu_conv_plca_backward: the three gradients of the PLCA reconstructions (plca.py:371-373, 447-449,
+ * 522-525, 602-605) given g = d loss / d out:
+ *   dense   out[m][k] = sum_r h[m][r] z[r] w[k][r]                         g, ld, m, k, rank as nmfmu_reconstruct_backward
+ *   conv    out = convNd(h, (w z).flip(..), padding = taps - 1)            g, w, h, batch .. taps as nmfmu_conv_backward
+ * z (rank floats) indexes the rank axis, which no product contracts, so with the UNSCALED products
+ *   rawH = g w  resp.  sum_c sum_t w[c][r][t] g[b][c][j + t]              rawW = g^T h  resp.  sum_b sum_j g[b][c][j + t] h[b][r][j]
+ * (exactly what nmfmu_reconstruct_backward / nmfmu_conv_backward compute, by the same kernels, split rule and part order)
+ *   grad_h[..][r][..] = z[r] rawH[..][r][..]        grad_w[c][r][..] = z[r] rawW[c][r][..]
+ *   grad_z[r] = sum rawW[c][r][t] w[c][r][t]  ( = sum rawH[b][r][j] h[b][r][j] )
+ * No w z temporary is built.  g, h, w, z must all be given; any of grad_h / grad_w / grad_z may be NULL (not all three).
+ * Half selection.  The H half (rawH) is launched iff grad_h is wanted.  grad_z comes from the H half iff grad_h is wanted and
+ * grad_w is not; otherwise from the W half.  The W half (rawW) is launched iff grad_w is wanted, or grad_z is wanted and grad_h
+ * is not (then, with grad_w NULL, its raw product lives in ws only).
+ * Finishing kernel.  Each launched half is finished in ONE pass over its output seen as [outer][rank][inner] (dense: outer = m
+ * resp. k, inner = 1; conv: outer = batch resp. channels, inner = prod(lh) resp. prod(taps)): it adds the half's parts in part
+ * order (in place of the slab-sum pass of the two entries above; with one part it runs in place over the product's output),
+ * multiplies by z[r], stores the gradient if wanted, and, for the half grad_z comes from, accumulates sum raw F per rank against
+ * the factor F of the output's layout.  Workgroup rule (a pure function of outer, rank, inner):
+ *   want  = min(2048, ceil(outer rank inner / 8192))
+ *   chunk = ceil(outer / min(want, outer));  nbo = ceil(outer / chunk)                     outer indices per workgroup
+ *   inner == 1: nseg = 1;  else ns = max(1, min(ceil(want / nbo), floor(inner / 1024))),
+ *               seg = ceil(inner / ns) rounded up to a multiple of 4,  nseg = ceil(inner / seg)   inner positions per workgroup
+ *   blocks = nbo nseg; workgroup (x, y) owns outer [x chunk, (x + 1) chunk) and inner [y seg, (y + 1) seg), block index y nbo + x.
+ * Every thread owns fixed ranks and a fixed sequence of elements; one thread per rank adds the workgroup's thread sums in
+ * thread order; the [blocks][rank] partials in ws are added in block order by a second small kernel.  No floating-point
+ * atomics, no fences: bit-identical run to run.  16-byte accesses where rows / lines are 16-byte aligned (rank resp. inner a
+ * multiple of 4, aligned pointers), scalar otherwise.
+ * ws (floats):  [H half: parts_h outer rank inner, if parts_h > 1]  [W half: parts_w outer rank inner, if parts_w > 1 or grad_w
+ * is NULL]  [blocks rank of the half grad_z comes from, if grad_z is wanted]; the first two regions are rounded up to a multiple
+ * of 4 floats each, so that every region of a 16-byte aligned ws is 16-byte aligned.
+ * The _ws functions (host only) return the floats ws must hold (0: ws may be NULL) or NMFMU_ERR_ARG, and, when info is not NULL,
+ *   info[0] = parts of the H half, info[1] = parts of the W half (0: not launched), info[2] / info[3] = finishing workgroups
+ *   of the H / W half (0: not launched), info[4] = the half grad_z comes from (0 none, 1 H, 2 W).
+ * Argument checks as the two entries above: NULL inputs, non-positive sizes, ld < k, flattened conv axes above 2^30, a missing
+ * ws: NMFMU_ERR_ARG, before any device work. */
+int64_t nmfmu_plca_backward_ws(int m, int k, int rank, int want_h, int want_w, int want_z, int* info);
+int nmfmu_plca_backward(const float* g, int64_t ld, int m, int k, const float* h, const float* w, const float* z, int rank,
+                        float* grad_h, float* grad_w, float* grad_z, float* ws, void* stream);
+int64_t nmfmu_conv_plca_backward_ws(int batch, int channels, int rank, int ndim, const int32_t* lh, const int32_t* taps,
+                                    int want_h, int want_w, int want_z, int* info);
+int nmfmu_conv_plca_backward(const float* g, const float* w, const float* h, const float* z, int batch, int channels, int rank,
+                             int ndim, const int32_t* lh, const int32_t* taps, float* grad_h, float* grad_w, float* grad_z,
+                             float* ws, void* stream);
 
 /* nmfmu_hoyer_project: Hoyer's projection onto {v >= 0, sum v = k1, sum v^2 = k2} (Hoyer 2004, section 3.3; the reference's
  * nmf.py:21-49) of every slice of a factor, in place, in ONE call with no host round trip.  x is a contiguous fp32 tensor seen

@@ -159,17 +159,24 @@ int launch_slab_sum(const float* slab, int nslab, int64_t plane, float* out, hip
   return (int)hipGetLastError();
 }
 
-static int backward_half(bool trans, const float* G, int64_t ld, int rows, int C, const float* B, int R, float* out,
-                         float* slab, hipStream_t s) {
+// The product kernel of one half alone: its backward_nsplit(rows, C, R) parts go to dst -- [parts][rows][R] partial products,
+// i.e. the output itself when there is one part.  The caller sums the parts (backward_half; nmfmu_plca_autograd.hip).
+int launch_backward_product(bool trans, const float* G, int64_t ld, int rows, int C, const float* B, int R, float* dst,
+                            hipStream_t s) {
   const int nsplit = backward_nsplit(rows, C, R);
   const int part_len = backward_part_len(C, nsplit);
   dim3 grid((rows + 127) / 128, (R + 127) / 128, nsplit);
-  float* dst = nsplit > 1 ? slab : out;
   if (trans)
     hipLaunchKernelGGL(reconstruct_backward_kernel<true>, grid, dim3(256), 0, s, G, ld, rows, C, B, R, part_len, dst);
   else
     hipLaunchKernelGGL(reconstruct_backward_kernel<false>, grid, dim3(256), 0, s, G, ld, rows, C, B, R, part_len, dst);
-  int e = (int)hipGetLastError();
+  return (int)hipGetLastError();
+}
+
+static int backward_half(bool trans, const float* G, int64_t ld, int rows, int C, const float* B, int R, float* out,
+                         float* slab, hipStream_t s) {
+  const int nsplit = backward_nsplit(rows, C, R);
+  int e = launch_backward_product(trans, G, ld, rows, C, B, R, nsplit > 1 ? slab : out, s);
   if (e || nsplit == 1) return e;
   return launch_slab_sum(slab, nsplit, (int64_t)rows * R, out, s);
 }

@@ -70,6 +70,27 @@ int64_t conv_backward_ws_floats(int batch, int channels, int rank, int ndim, con
                                 bool want_w, int* splits);
 int launch_conv_backward(const float* G, const float* W, const float* H, int batch, int channels, int rank, int ndim,
                          const int32_t* lh, const int32_t* taps, float* grad_h, float* grad_w, float* ws, hipStream_t st);
+// the product kernel of ONE half alone (no slab sum): backward_nsplit parts to dst = [parts][output]
+int launch_backward_product(bool trans, const float* G, int64_t ld, int rows, int C, const float* B, int R, float* dst,
+                            hipStream_t s);
+int launch_conv_backward_product(bool w_half, const float* G, const float* F, int batch, int channels, int rank, int ndim,
+                                 const int32_t* lh, const int32_t* taps, float* dst, hipStream_t st);
+// nmfmu_plca_autograd.hip: backward of the PLCA / SIPLCA reconstructions (H, W, Z).  plca_finish_grid is the workgroup rule of
+// the finishing kernel over an output [outer][rank][inner] (include/nmfmu.h states it): nbo chunks of `chunk` outer indices
+// times nseg segments of `seg` inner positions.  info: {parts H, parts W, blocks H, blocks W, half of grad_Z (0 / 1 = H / 2 = W)}.
+struct PlcaFinishGrid {
+  int nbo, chunk, nseg, seg;
+  int blocks() const { return nbo * nseg; }
+};
+PlcaFinishGrid plca_finish_grid(int64_t outer, int rank, int64_t inner);
+int64_t plca_backward_ws_floats(int m, int k, int rank, bool want_h, bool want_w, bool want_z, int* info);
+int launch_plca_backward(const float* G, int64_t ld, int m, int k, const float* H, const float* W, const float* Z, int rank,
+                         float* grad_h, float* grad_w, float* grad_z, float* ws, hipStream_t s);
+int64_t conv_plca_backward_ws_floats(int batch, int channels, int rank, int ndim, const int32_t* lh, const int32_t* taps,
+                                     bool want_h, bool want_w, bool want_z, int* info);
+int launch_conv_plca_backward(const float* G, const float* W, const float* H, const float* Z, int batch, int channels, int rank,
+                              int ndim, const int32_t* lh, const int32_t* taps, float* grad_h, float* grad_w, float* grad_z,
+                              float* ws, hipStream_t s);
 int launch_probe_mfma(const uint16_t* a, const uint16_t* b, float* d, hipStream_t s);
 int launch_probe_lds_dma(const uint32_t* src, uint32_t* dst, int n_dwords, hipStream_t s);
 int launch_ubench_mfma_hbm(const void* operands, size_t operand_bytes, int f16, const void* stream_src, int kib_per_tile,

@@ -592,6 +592,36 @@ int nmfmu_conv_backward(const float* g, const float* w, const float* h, int batc
   return launch_conv_backward(g, w, h, batch, channels, rank, ndim, lh, taps, grad_h, grad_w, ws, S(stream));
 }
 
+int64_t nmfmu_plca_backward_ws(int m, int k, int rank, int want_h, int want_w, int want_z, int* info) {
+  if (m <= 0 || k <= 0 || rank <= 0) return NMFMU_ERR_ARG;
+  return plca_backward_ws_floats(m, k, rank, want_h != 0, want_w != 0, want_z != 0, info);
+}
+
+int nmfmu_plca_backward(const float* g, int64_t ld, int m, int k, const float* h, const float* w, const float* z, int rank,
+                        float* grad_h, float* grad_w, float* grad_z, float* ws, void* stream) {
+  if (!g || !h || !w || !z || m <= 0 || k <= 0 || rank <= 0 || ld < k) return NMFMU_ERR_ARG;
+  if (!grad_h && !grad_w && !grad_z) return NMFMU_ERR_ARG;
+  if (!ws && plca_backward_ws_floats(m, k, rank, grad_h != nullptr, grad_w != nullptr, grad_z != nullptr, nullptr) > 0)
+    return NMFMU_ERR_ARG;
+  return launch_plca_backward(g, ld, m, k, h, w, z, rank, grad_h, grad_w, grad_z, ws, S(stream));
+}
+
+int64_t nmfmu_conv_plca_backward_ws(int batch, int channels, int rank, int ndim, const int32_t* lh, const int32_t* taps,
+                                    int want_h, int want_w, int want_z, int* info) {
+  const int64_t n = conv_plca_backward_ws_floats(batch, channels, rank, ndim, lh, taps, want_h != 0, want_w != 0, want_z != 0, info);
+  return n < 0 ? NMFMU_ERR_ARG : n;
+}
+
+int nmfmu_conv_plca_backward(const float* g, const float* w, const float* h, const float* z, int batch, int channels, int rank,
+                             int ndim, const int32_t* lh, const int32_t* taps, float* grad_h, float* grad_w, float* grad_z,
+                             float* ws, void* stream) {
+  if (!g || !w || !h || !z || (!grad_h && !grad_w && !grad_z)) return NMFMU_ERR_ARG;
+  const int64_t n = conv_plca_backward_ws_floats(batch, channels, rank, ndim, lh, taps, grad_h != nullptr, grad_w != nullptr,
+                                                 grad_z != nullptr, nullptr);
+  if (n < 0 || (n > 0 && !ws)) return NMFMU_ERR_ARG;
+  return launch_conv_plca_backward(g, w, h, z, batch, channels, rank, ndim, lh, taps, grad_h, grad_w, grad_z, ws, S(stream));
+}
+
 int nmfmu_beta_div_grad(const float* x, const float* y, int64_t n, float beta, const float* upstream, float* gx,
                         void* stream) {
   if (!x || !y || !upstream || !gx || n < 0) return NMFMU_ERR_ARG;

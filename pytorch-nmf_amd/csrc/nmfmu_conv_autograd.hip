@@ -167,17 +167,23 @@ ConvAxis conv_axis(int64_t n, const int* d, int64_t gstride) {
   return ConvAxis{(int)n, d[0] * d[1] * d[2], d[1], d[2], gstride};
 }
 
-int conv_backward_half(const float* G, const float* F, const ConvAxis& o, const ConvAxis& k, int R, const ConvShape& s, float* out,
-                       float* slab, hipStream_t st) {
+// the product kernel alone: backward_nsplit(o.n, k.n, R) parts to dst ([parts][output]; the output itself with one part)
+int conv_backward_product(const float* G, const float* F, const ConvAxis& o, const ConvAxis& k, int R, const ConvShape& s,
+                          float* dst, hipStream_t st) {
   const int nsplit = backward_nsplit(o.n, k.n, R);
   ConvBackwardArgs a{o, k, R, s.lh[1] + s.taps[1] - 1, s.lh[2] + s.taps[2] - 1, backward_part_len(k.n, nsplit)};
-  float* dst = nsplit > 1 ? slab : out;
   if (R <= 32)
     hipLaunchKernelGGL(conv_backward_kernel<32>, dim3((o.n + kCvBO - 1) / kCvBO, 1, nsplit), dim3(256), 0, st, G, F, a, dst);
   else
     hipLaunchKernelGGL(conv_backward_kernel<128>, dim3((o.n + kCvBO - 1) / kCvBO, (R + 127) / 128, nsplit), dim3(256), 0, st,
                        G, F, a, dst);
-  int e = (int)hipGetLastError();
+  return (int)hipGetLastError();
+}
+
+int conv_backward_half(const float* G, const float* F, const ConvAxis& o, const ConvAxis& k, int R, const ConvShape& s, float* out,
+                       float* slab, hipStream_t st) {
+  const int nsplit = backward_nsplit(o.n, k.n, R);
+  int e = conv_backward_product(G, F, o, k, R, s, nsplit > 1 ? slab : out, st);
   if (e || nsplit == 1) return e;
   return launch_slab_sum(slab, nsplit, (int64_t)R * o.n, out, st);
 }
@@ -208,6 +214,16 @@ int launch_conv_backward(const float* G, const float* W, const float* H, int bat
   }
   if (grad_w) return conv_backward_half(G, H, ct, bj, rank, s, grad_w, slab_w, st);
   return 0;
+}
+
+// One half's product kernel alone (w_half: grad_w's, F = H; else grad_h's, F = W), its parts to dst: what
+// nmfmu_plca_autograd.hip finishes itself.  -1 for the sizes conv_backward_ws_floats rejects.
+int launch_conv_backward_product(bool w_half, const float* G, const float* F, int batch, int channels, int rank, int ndim,
+                                 const int32_t* lh, const int32_t* taps, float* dst, hipStream_t st) {
+  ConvShape s;
+  if (!conv_shape(batch, channels, rank, ndim, lh, taps, &s)) return -1;
+  const ConvAxis bj = conv_axis(s.bj, s.lh, (int64_t)channels * s.pl), ct = conv_axis(s.ct, s.taps, s.pl);
+  return w_half ? conv_backward_product(G, F, ct, bj, rank, s, dst, st) : conv_backward_product(G, F, bj, ct, rank, s, dst, st);
 }
 
 }  // namespace nmfmu

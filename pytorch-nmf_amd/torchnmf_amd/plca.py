@@ -297,6 +297,58 @@ def plain_struct(fb: FactorBuf):
     return ctypes.byref(fb.struct)
 
 
+def _dptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _plca_forward(H: Tensor, W: Tensor, Z: Tensor) -> Tensor:
+    from .nmf import NMF
+    return NMF.reconstruct(H.detach(), W.detach() * Z.detach())
+
+
+def _plca_backward(G: Tensor, H: Tensor, W: Tensor, Z: Tensor, need_h: bool, need_w: bool, need_z: bool):
+    """(grad_H | None, grad_W | None, grad_Z | None) of ``out = H @ (W * Z).T`` given ``G = d loss / d out``, in the inputs'
+    shapes and dtypes: one ``nmfmu_plca_backward`` call.  ``G`` is read in place through its row stride; only a last stride
+    other than 1 costs a copy (the rule of the NMF backward)."""
+    lib = _capi.load()
+    R, C = H.shape[-1], W.shape[0]
+    Hc = H.detach().float().reshape(-1, R).contiguous()
+    Wc, Zc = W.detach().float().contiguous(), Z.detach().float().contiguous()
+    N = Hc.shape[0]
+    G2 = G.detach().float().reshape(N, C)
+    if G2.stride(1) != 1 or (N > 1 and G2.stride(0) < C):
+        G2 = G2.contiguous()
+    ld = G2.stride(0) if N > 1 else C
+    dev = G2.device
+    gH = torch.empty(N, R, dtype=torch.float32, device=dev) if need_h else None
+    gW = torch.empty(C, R, dtype=torch.float32, device=dev) if need_w else None
+    gZ = torch.empty(R, dtype=torch.float32, device=dev) if need_z else None
+    n_ws = lib.nmfmu_plca_backward_ws(N, C, R, int(need_h), int(need_w), int(need_z), None)
+    _capi.check(min(n_ws, 0), 'nmfmu_plca_backward_ws')
+    ws = torch.empty(n_ws, dtype=torch.float32, device=dev) if n_ws > 0 else None
+    _capi.check(lib.nmfmu_plca_backward(G2.data_ptr(), ld, N, C, Hc.data_ptr(), Wc.data_ptr(), Zc.data_ptr(), R, _dptr(gH),
+                                        _dptr(gW), _dptr(gZ), _dptr(ws), torch.cuda.current_stream().cuda_stream),
+                'nmfmu_plca_backward')
+    return ((gH.reshape(H.shape).to(H.dtype) if need_h else None), (gW.to(W.dtype) if need_w else None),
+            (gZ.to(Z.dtype) if need_z else None))
+
+
+class _PlcaReconstructFn(torch.autograd.Function):
+    """``PLCA.reconstruct`` with a device backward.  The forward is the ``W * Z`` product and the ``nmfmu_reconstruct`` launch
+    of the path without autograd (bit-identical output)."""
+
+    @staticmethod
+    def forward(ctx, H, W, Z):
+        ctx.save_for_backward(H, W, Z)
+        return _plca_forward(H, W, Z)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, G):
+        H, W, Z = ctx.saved_tensors
+        return _plca_backward(G, H, W, Z, *ctx.needs_input_grad[:3])
+
+
 class PLCA(BaseComponent):
     """``V ~ H diag(Z) W^T`` with V (N, C), W (C, R), H (N, R), Z (R,) (reference: plca.py:311-373)."""
 
@@ -310,9 +362,18 @@ class PLCA(BaseComponent):
 
     @staticmethod
     def reconstruct(H: Tensor, W: Tensor, Z: Tensor) -> Tensor:
-        """``H @ (W * Z).T`` (plca.py:371-373) on the device (exact-fp32 MFMA kernel of NMF.reconstruct)."""
-        from .nmf import NMF
-        return NMF.reconstruct(H.detach(), W.detach() * Z.detach())      # (PLCA stays outside autograd)
+        """``H @ (W * Z).T`` (plca.py:371-373) on the device (exact-fp32 MFMA kernel of NMF.reconstruct).
+
+        Differentiable like the reference's ``F.linear``: with grad mode on and ``H``, ``W`` or ``Z`` requiring grad the
+        result carries a ``grad_fn`` whose backward is one ``nmfmu_plca_backward`` call (first order only).  Under
+        ``torch.no_grad()`` -- ``fit()`` -- nothing is recorded."""
+        if torch.is_grad_enabled() and (H.requires_grad or W.requires_grad or Z.requires_grad):
+            _require_device(H, 'reconstruct')
+            _require_device(W, 'reconstruct')
+            _require_device(Z, 'reconstruct')
+            assert H.dim() >= 2 and W.dim() == 2 and Z.dim() == 1 and H.shape[-1] == W.shape[1] == Z.shape[0]
+            return _PlcaReconstructFn.apply(H, W, Z)
+        return _plca_forward(H, W, Z)
 
     def _make_em(self, Vn, precision):
         assert Vn.dim() == 2 and Vn.shape == (self.H.shape[0], self.W.shape[0])
@@ -418,6 +479,46 @@ def _conv_reconstruct(H: Tensor, W: Tensor, Z: Tensor) -> Tensor:
     return reconstruct(H, W.detach() * Z.detach().view(1, -1, *([1] * (W.dim() - 2))))
 
 
+def _conv_plca_backward(G: Tensor, H: Tensor, W: Tensor, Z: Tensor, need_h: bool, need_w: bool, need_z: bool):
+    """(grad_H | None, grad_W | None, grad_Z | None) of the shift-invariant reconstruction given ``G = d loss / d out``, in the
+    inputs' shapes and dtypes: one ``nmfmu_conv_plca_backward`` call.  A contiguous fp32 ``G`` is read in place; anything else
+    is copied once (the rule of the NMFD backward)."""
+    import ctypes
+    lib = _capi.load()
+    Hc, Wc, Zc = H.detach().float().contiguous(), W.detach().float().contiguous(), Z.detach().float().contiguous()
+    Gc = G.detach().float().contiguous()
+    nd = Hc.dim() - 2
+    B, R, Cc = Hc.shape[0], Hc.shape[1], Wc.shape[0]
+    lh, taps = (ctypes.c_int32 * nd)(*Hc.shape[2:]), (ctypes.c_int32 * nd)(*Wc.shape[2:])
+    assert tuple(Gc.shape) == (B, Cc) + tuple(a + t - 1 for a, t in zip(Hc.shape[2:], Wc.shape[2:]))
+    gH = torch.empty_like(Hc) if need_h else None
+    gW = torch.empty_like(Wc) if need_w else None
+    gZ = torch.empty_like(Zc) if need_z else None
+    n_ws = lib.nmfmu_conv_plca_backward_ws(B, Cc, R, nd, lh, taps, int(need_h), int(need_w), int(need_z), None)
+    _capi.check(min(n_ws, 0), 'nmfmu_conv_plca_backward_ws')
+    ws = torch.empty(n_ws, dtype=torch.float32, device=Gc.device) if n_ws > 0 else None
+    _capi.check(lib.nmfmu_conv_plca_backward(Gc.data_ptr(), Wc.data_ptr(), Hc.data_ptr(), Zc.data_ptr(), B, Cc, R, nd, lh, taps,
+                                             _dptr(gH), _dptr(gW), _dptr(gZ), _dptr(ws),
+                                             torch.cuda.current_stream().cuda_stream), 'nmfmu_conv_plca_backward')
+    return ((gH.to(H.dtype) if need_h else None), (gW.to(W.dtype) if need_w else None), (gZ.to(Z.dtype) if need_z else None))
+
+
+class _ConvPlcaReconstructFn(torch.autograd.Function):
+    """``SIPLCA / SIPLCA2 / SIPLCA3.reconstruct`` with a device backward.  The forward is ``_conv_reconstruct`` itself: the same
+    launches as without autograd (bit-identical output)."""
+
+    @staticmethod
+    def forward(ctx, H, W, Z):
+        ctx.save_for_backward(H, W, Z)
+        return _conv_reconstruct(H, W, Z)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, G):
+        H, W, Z = ctx.saved_tensors
+        return _conv_plca_backward(G, H, W, Z, *ctx.needs_input_grad[:3])
+
+
 class _ShiftInvariant(BaseComponent):
     def _make_em(self, Vn, precision):
         assert Vn.dim() == self.W.dim() and Vn.shape[0] == self.H.shape[0] and Vn.shape[1] == self.W.shape[0]
@@ -428,7 +529,16 @@ class _ShiftInvariant(BaseComponent):
 
     @staticmethod
     def reconstruct(H: Tensor, W: Tensor, Z: Tensor) -> Tensor:
-        """``convNd(H, W.flip * Z, padding = T - 1)`` (plca.py:447-449, 522-525, 602-605)."""
+        """``convNd(H, W.flip * Z, padding = T - 1)`` (plca.py:447-449, 522-525, 602-605).
+
+        Differentiable like the reference's convolution: with grad mode on and ``H``, ``W`` or ``Z`` requiring grad the result
+        carries a ``grad_fn`` whose backward is one ``nmfmu_conv_plca_backward`` call (first order only).  Under
+        ``torch.no_grad()`` -- ``fit()`` -- nothing is recorded."""
+        if torch.is_grad_enabled() and (H.requires_grad or W.requires_grad or Z.requires_grad):
+            _require_device(H, 'reconstruct')
+            _require_device(W, 'reconstruct')
+            _require_device(Z, 'reconstruct')
+            return _ConvPlcaReconstructFn.apply(H, W, Z)
         return _conv_reconstruct(H, W, Z)
 
 
