@@ -713,6 +713,36 @@ size_t nmfmu_gram_part_bytes(int rank);   /* scratch of nmfmu_gram */
 int nmfmu_gram(const float* f, int rows, int rank, float* part, float* gram, void* stream);
 int nmfmu_rowmat(const float* owner, int rows, int rank, const float* gram, float* den, int r_pad, void* stream);
 
+/* ---- autograd on sparse-COO targets: V_norm + pos - neg and its factor gradients, beta in {1, 2} (additive entries) --------
+ * Built on SEGMENTS, not whole owner rows: the host cuts every CSR row (H side, forward) and every CSC column (W side) into
+ * runs of at most `chunk` stored entries and one wave takes one run, so a few rows with thousands of entries do not set
+ * the run time.
+ *   seg   int32 [n_seg][4] = (owner row, p_begin, p_end, slot), in row order.  slot < 0: the row's only segment (a row without
+ *         entries has one empty segment: every owner row belongs to exactly one writer).  slot >= 0: the row is split; the
+ *         segment's partial row is stored to ws[slot][r_pad]; the slots of a row are consecutive and in segment order
+ *   multi int32 [n_multi][3] = (owner row, first slot, number of segments) of the split rows
+ *   nmfmu_sp_div_backward_ws : floats of `ws` = (sum of `segments` over multi) * r_pad -- a pure function of the counts
+ *   nmfmu_sp_div_forward     : *out = sum over the stored entries of v log(s + eps) (beta 1) | v s (beta 2),
+ *                              s = <owner[row], panel[colidx[p]]>; accumulated in double per wave, per workgroup, then in
+ *                              block order.  part: (n_seg + 3) / 4 doubles of scratch.  s_out (may be NULL): s[p] for
+ *                              every stored entry, in the order of colidx (what the beta == 1 backward reads)
+ *   nmfmu_sp_div_backward    : out[row][:] = up[0] * (pos - sum over the row's entries of g * panel[idx[p]][:]),
+ *                              g = vals[p] / (s[q] + eps) (beta 1; q = perm ? perm[p] : p) | vals[p] (beta 2; s, perm unused).
+ *                              One call per side: the H side takes the CSR list (perm NULL), the W side the CSC list with
+ *                              vals in CSC order and perm[p] = the CSR position of CSC entry p.  pos: a vector [rank]
+ *                              (pos_plane == 0; beta 1: the panel's column sums, nmfmu_rank_sums) or a plane [rows][r_pad]
+ *                              (pos_plane != 0; beta 2: nmfmu_rowmat of the owner and the panel's Gram matrix).  up: the 0-dim
+ *                              incoming gradient, read on the device.  out is [owner rows][r_pad]; every padded column is
+ *                              written (0).  Entries accumulate in storage order, a split row's partials in segment order:
+ *                              plain stores only, no atomics -- a repeated call is bitwise identical.
+ * Other beta: NMFMU_ERR_UNSUPPORTED.  rank <= 256. */
+int64_t nmfmu_sp_div_backward_ws(int n_multi_segments, int r_pad);
+int nmfmu_sp_div_forward(const int32_t* seg, int n_seg, const int32_t* colidx, const float* vals, const float* owner,
+                         const float* panel, int rank, float beta, float* s_out, double* part, double* out, void* stream);
+int nmfmu_sp_div_backward(const int32_t* seg, int n_seg, const int32_t* multi, int n_multi, const int32_t* idx,
+                          const float* vals, const int32_t* perm, const float* s, const float* panel, int rank, float beta,
+                          const float* pos, int pos_plane, const float* up, float* ws, float* out, int r_pad, void* stream);
+
 /* ---- PLCA's EM update (plca.py:248-290) -----------------------------------------------------------------------------
  * With G = Vn / (H diag(Z) W^T + eps) the factor "gradients" are (G^T H) * Z, (G W) * Z and Z.grad[r] = sum W * (G^T H);
  * nmfmu_mu_partial delivers the unscaled numerators G^T H / G W when the step's panel struct carries the image of the

@@ -8,6 +8,11 @@ there is no CPU path.  The divergences are differentiable with respect to
 carries a ``grad_fn`` whose backward is one elementwise HIP kernel
 (``nmfmu_beta_div_grad``).  ``target`` is always a constant: no gradient flows
 to it, whether or not it requires grad.
+
+``sparse_beta_div(H, W, target, beta)`` is the same divergence between
+``H @ W.T`` and a sparse-COO target, computed from the stored entries only
+(beta in {1, 2}; ``sparse_autograd.py``): differentiable with respect to both
+factors, with HIP backward kernels (``nmfmu_sp_div_backward``).
 """
 from __future__ import annotations
 
@@ -15,8 +20,9 @@ import torch
 from torch import Tensor
 
 from . import _capi
+from .sparse_autograd import SparseTarget, sparse_beta_div
 
-__all__ = ['kl_div', 'euclidean', 'is_div', 'beta_div', 'sparseness']
+__all__ = ['kl_div', 'euclidean', 'is_div', 'beta_div', 'sparseness', 'SparseTarget', 'sparse_beta_div']
 
 
 def _beta_div_value(input: Tensor, target: Tensor, beta: float) -> Tensor:

@@ -279,8 +279,10 @@ class BaseComponent(nn.Module):
                 raise NotImplementedError(f'sparse_fit has no CPU path: tensors live on {t.device}; torchnmf_amd computes '
                                           f'on an MI355X only -- move the module and its target with .cuda()')
         if V.is_sparse:
-            raise NotImplementedError('sparse_fit: sparse-COO targets are not implemented (dense targets only); use '
-                                      'V.to_dense(), or NMF.fit for the multiplicative update on a sparse target')
+            raise NotImplementedError('sparse_fit: sparse-COO targets are not implemented (dense targets only); for a Hoyer-'
+                                      'constrained fit on a sparse target drive trainer.SparsityProj with the closure '
+                                      'metrics.sparse_beta_div(m.H, m.W, SparseTarget(V), beta) (beta in {1, 2}); otherwise '
+                                      'use V.to_dense(), or NMF.fit for the multiplicative update on a sparse target')
         if W.dtype != torch.float32 or H.dtype != torch.float32:
             if not (W.dtype.is_floating_point and H.dtype.is_floating_point):
                 raise NotImplementedError(f'factors must be floating point; got W {W.dtype}, H {H.dtype}')
