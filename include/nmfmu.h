@@ -58,7 +58,9 @@ extern "C" {
                                   trainer.SparsityProj);
                                   nmfmu_plca_backward / nmfmu_plca_backward_ws / nmfmu_conv_plca_backward /
                                   nmfmu_conv_plca_backward_ws (torch.autograd through PLCA / SIPLCA / SIPLCA2 / SIPLCA3.forward:
-                                  the two products above, finished with the latent vector Z) */
+                                  the two products above, finished with the latent vector Z);
+                                  nmfmu_sp_masked_terms / nmfmu_sp_masked_step / nmfmu_sp_masked_loss / nmfmu_sp_masked_ws
+                                  (missing-data NMF: sparse targets fitted over their stored entries only, every beta) */
 
 #define NMFMU_OK 0
 #define NMFMU_ERR_UNSUPPORTED (-2) /* rank / precision / beta combination not built */
@@ -742,6 +744,37 @@ int nmfmu_sp_div_forward(const int32_t* seg, int n_seg, const int32_t* colidx, c
 int nmfmu_sp_div_backward(const int32_t* seg, int n_seg, const int32_t* multi, int n_multi, const int32_t* idx,
                           const float* vals, const int32_t* perm, const float* s, const float* panel, int rank, float beta,
                           const float* pos, int pos_plane, const float* up, float* ws, float* out, int r_pad, void* stream);
+
+/* ---- missing-data NMF: a sparse target fitted over its STORED entries only, every beta (additive entries) ---------------------
+ * The unstored entries are unknown, not zero: both contractions of the multiplicative update run over the stored set,
+ *   s_p = <owner[row], panel[idx[p]]>,  num[row] = sum_p g_neg(v_p, s_p) panel[idx[p]],  den[row] = sum_p g_pos(s_p) panel[idx[p]]
+ * with g_neg / g_pos = output_neg / output_pos of nmf.py:61-74 (beta 2: v, s; beta 1: v / (s + eps), 1; beta 0: v / (s + eps)^2,
+ * 1 / (s + eps); otherwise v (s + eps)^(beta - 2), (s + eps)^(beta - 1)).  seg / multi are the segment lists of
+ * nmfmu_sp_div_backward; one call per side: the H side takes the CSR list, the W side the CSC list with vals in CSC order.
+ * Entries accumulate in storage order, a split row's partial [num | den] rows (ws[slot][2 r_pad]) in segment order: plain
+ * stores only, no atomics -- a repeated call is bitwise identical.
+ *   nmfmu_sp_masked_ws    : floats of `ws` = (sum of `segments` over multi) * 2 * r_pad -- a pure function of the counts
+ *   nmfmu_sp_masked_terms : num, den [owner rows][r_pad]; every padded column is written (0); a row without entries gets zeros.
+ *                           den - num is the gradient of the masked loss with respect to the owner.
+ *   nmfmu_sp_masked_step  : the same terms, then nmf.py:78-92 in place on the owner's fp32 master [owner rows][rank]:
+ *                           f *= ((relu(num) + eps) / (relu(den) + eps + l1 + l2 f))^gamma.  owner != panel.
+ *   nmfmu_sp_masked_loss  : *out = metrics.beta_div(s, v, beta) over the stored entries (seg: the CSR list, owner = H), with the
+ *                           reference's eps conventions per branch (metrics.py:22, 39, 57, 85-96).  The terms that hold s are
+ *                           summed in double per wave, per workgroup, then in block order; v_term carries the terms of v alone,
+ *                           formed by the caller in float64: beta 2: 0; beta 1: sum v log(v + eps) - sum v; beta 0:
+ *                           -sum log(v + eps) - nnz; otherwise sum v'^beta (v' = v + eps when beta < 0, else v).
+ *                           part: (n_seg + 3) / 4 doubles of scratch.
+ * Null pointers, n_seg <= 0, rank <= 0, r_pad != nmfmu_pad_rank(rank): NMFMU_ERR_ARG; rank > 256: NMFMU_ERR_UNSUPPORTED -- both
+ * before any device work. */
+int64_t nmfmu_sp_masked_ws(int n_multi_segments, int r_pad);
+int nmfmu_sp_masked_terms(const int32_t* seg, int n_seg, const int32_t* multi, int n_multi, const int32_t* idx,
+                          const float* vals, const float* owner, const float* panel, int rank, float beta, float* ws,
+                          float* num, float* den, int r_pad, void* stream);
+int nmfmu_sp_masked_step(const int32_t* seg, int n_seg, const int32_t* multi, int n_multi, const int32_t* idx,
+                         const float* vals, float* owner, const float* panel, int rank, float beta, float l1, float l2,
+                         float gamma, float* ws, int r_pad, void* stream);
+int nmfmu_sp_masked_loss(const int32_t* seg, int n_seg, const int32_t* colidx, const float* vals, const float* owner,
+                         const float* panel, int rank, float beta, double v_term, double* part, double* out, void* stream);
 
 /* ---- PLCA's EM update (plca.py:248-290) -----------------------------------------------------------------------------
  * With G = Vn / (H diag(Z) W^T + eps) the factor "gradients" are (G^T H) * Z, (G W) * Z and Z.grad[r] = sum W * (G^T H);

@@ -12,7 +12,10 @@ to it, whether or not it requires grad.
 ``sparse_beta_div(H, W, target, beta)`` is the same divergence between
 ``H @ W.T`` and a sparse-COO target, computed from the stored entries only
 (beta in {1, 2}; ``sparse_autograd.py``): differentiable with respect to both
-factors, with HIP backward kernels (``nmfmu_sp_div_backward``).
+factors, with HIP backward kernels (``nmfmu_sp_div_backward``).  With
+``unstored='missing'`` the unstored entries are unknown instead of zero: the
+reference's ``beta_div`` over the stored entries alone, for any beta
+(``nmfmu_sp_masked_loss`` / ``nmfmu_sp_masked_terms``).
 """
 from __future__ import annotations
 

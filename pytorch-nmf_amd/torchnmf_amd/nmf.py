@@ -380,7 +380,7 @@ class BaseComponent(nn.Module):
     @torch.no_grad()
     def fit(self, V: Tensor, beta: float = 1, tol: float = 1e-4, max_iter: int = 200, verbose: bool = False,
             alpha: float = 0, l1_ratio: float = 0, *, precision: Optional[str] = None, process_group=None,
-            allreduce: Optional[str] = None) -> int:
+            allreduce: Optional[str] = None, unstored: str = 'zero') -> int:
         """Minimise the beta-divergence between ``V`` and the model by multiplicative updates.
 
         Same contract as the reference (nmf.py:297-409): W half-step, then H
@@ -413,7 +413,21 @@ class BaseComponent(nn.Module):
                          None = TORCHNMF_AMD_AR_OVERLAP / TORCHNMF_AMD_COMM; default 'single' over torch.distributed, the
                          form BASELINE's north_star names (round 5: 'overlap' was the default before, with no N > 1
                          measurement behind it).  'direct' raises when the backend has no communicator entry.
+          unstored       sparse targets only: 'zero' (default) counts every unstored entry as an observed zero, like the
+                         reference.  'missing' fits the STORED entries only -- ratings, unsampled pairs, masked bins: numerator
+                         and denominator of the update and the tracked loss (``beta_div`` over the stored entries) run over
+                         the stored set, O(nnz * rank) for every beta; beta <= 0 is admitted when the stored values are
+                         strictly positive.  Exact fp32: ``precision`` is ignored and ``last_precision`` is 'fp32'.  A dense
+                         target with a mask goes in as ``V.sparse_mask(mask)``.  NMF only, not sharded.
         """
+        if unstored not in ('zero', 'missing'):
+            raise ValueError(f"unstored must be 'zero' or 'missing', got {unstored!r}")
+        if unstored == 'missing':
+            if not V.is_sparse:
+                raise ValueError("unstored='missing' needs a sparse-COO target whose stored entries are the observed ones; "
+                                 "for a dense V with a boolean mask pass V.sparse_mask(mask) (mask: a sparse-COO tensor)")
+            if process_group is not None:
+                raise NotImplementedError("unstored='missing': sparse targets are not sharded")
         sparse = V.is_sparse
         if sparse and not isinstance(self, NMF):
             raise NotImplementedError('sparse targets are supported by NMF only (as in the reference)')
@@ -432,7 +446,7 @@ class BaseComponent(nn.Module):
             W.data, H.data = W.data.float().contiguous(), H.data.float().contiguous()
             try:
                 return self.fit(V, beta, tol, max_iter, verbose, alpha, l1_ratio, precision=precision,
-                                process_group=process_group, allreduce=allreduce)
+                                process_group=process_group, allreduce=allreduce, unstored=unstored)
             finally:
                 w32, h32 = W.data, H.data
                 W.data, H.data = keep
@@ -449,8 +463,13 @@ class BaseComponent(nn.Module):
         if sparse:
             if process_group is not None:
                 raise NotImplementedError('sparse targets are not sharded')
-            from .sparse_engine import SparseMU
-            eng = SparseMU(V, W.data, H.data, beta, l1, l2, update_W=W.requires_grad, update_H=H.requires_grad)
+            from .sparse_engine import MaskedMU, SparseMU
+            if unstored == 'missing':
+                if not (W.data.is_contiguous() and H.data.is_contiguous()):
+                    W.data, H.data = W.data.contiguous(), H.data.contiguous()
+                eng = MaskedMU(V, W.data, H.data, beta, l1, l2, update_W=W.requires_grad, update_H=H.requires_grad)
+            else:
+                eng = SparseMU(V, W.data, H.data, beta, l1, l2, update_W=W.requires_grad, update_H=H.requires_grad)
         else:
             if allreduce not in (None, 'single', 'overlap', 'direct'):
                 raise ValueError(f"allreduce must be None, 'single', 'overlap' or 'direct', got {allreduce!r}")

@@ -9,6 +9,13 @@ Only the stored entries of the target are touched: the dense ``N x C`` reconstru
             and the same with the roles swapped (``nmfmu_sp_div_backward``, once per wanted side; the beta == 2 planes from
             ``nmfmu_rowmat``)
 
+``unstored='missing'`` reads the target as missing data instead: its unstored entries are unknown, not zero, and the loss is
+the reference's ``beta_div`` over the stored entries alone -- any beta, O(nnz R):
+
+  forward   ``nmfmu_sp_masked_loss`` (the terms of v alone once per target on the host, float64)
+  backward  grad = up (den - num), the two planes of ``nmfmu_sp_masked_terms`` (one call per wanted side): the raw sums of
+            the masked multiplicative update, without its relu / eps
+
 The planning functions below are pure torch and run on CPU tensors as well; everything else needs the ROCm device.
 """
 from __future__ import annotations
@@ -85,6 +92,25 @@ def csr_csc(rows: Tensor, cols: Tensor, vals: Tensor, n_rows: int, n_cols: int):
     return csr, csc, perm.to(torch.int32).contiguous()
 
 
+def masked_workspace_floats(n_multi_segments: int, r_pad: int) -> int:
+    """The rule of ``nmfmu_sp_masked_ws``: one partial [num | den] row of ``2 r_pad`` floats per segment of a split row."""
+    return int(n_multi_segments) * 2 * int(r_pad) if n_multi_segments > 0 and r_pad > 0 else 0
+
+
+def masked_v_term(vals: Tensor, beta: float) -> float:
+    """The terms of ``metrics.beta_div(s, v, beta)`` that hold v alone (metrics.py:22, 39, 57, 85-96), in float64 -- what
+    ``nmfmu_sp_masked_loss`` takes as ``v_term``."""
+    from .constants import eps
+    vd = vals.double()
+    if beta == 2.0:
+        return 0.0
+    if beta == 1.0:
+        return float((vd @ (vd + eps).log() - vd.sum()).item())
+    if beta == 0.0:
+        return float((-(vd + eps).log().sum()).item()) - vd.numel()
+    return float((vd + eps if beta < 0 else vd).pow(beta).sum().item())
+
+
 def v_norm(vals: Tensor, beta: float) -> float:
     """nmf.py:172-181 over the stored values in float64, as ``SparseMU.__init__`` computes it."""
     vd = vals.double()
@@ -134,6 +160,28 @@ class SparseTarget:
         self.seg_w, self.multi_w, self.n_ws_w = plan_worklist(self.csc[0], self.chunk)
         self._no_entries = torch.zeros(4, dtype=torch.float32, device=V.device)
         self._v_norm = {}
+        self._has_zero = None
+
+    def side(self, side: str):
+        """((ptr, idx, vals), seg, multi, n_ws) of one side's work list: 'h' -- the CSR list, owner rows = rows of V; 'w' --
+        the CSC list, owner rows = columns of V, values in CSC order."""
+        if side == 'h':
+            return self.csr, self.seg_h, self.multi_h, self.n_ws_h
+        return self.csc, self.seg_w, self.multi_w, self.n_ws_w
+
+    @property
+    def has_zero(self) -> bool:
+        """Is a STORED value zero?  (Missing-data fits: unstored entries are not zeros.)  Once per target; one host sync."""
+        if self._has_zero is None:
+            self._has_zero = bool((self.vals == 0).any().item()) if self.nnz else False
+        return self._has_zero
+
+    def masked_v_term(self, beta: float) -> float:
+        """Once per (target, beta); a Python float."""
+        key = ('masked', beta)
+        if key not in self._v_norm:
+            self._v_norm[key] = masked_v_term(self.vals, beta)
+        return self._v_norm[key]
 
     def v_norm(self, beta: float) -> float:
         """Once per (target, beta); a Python float."""
@@ -226,6 +274,79 @@ def _backward_side(owner: Tensor, panel: Tensor, small_panel: Tensor, T: SparseT
     return out if r_pad == R else out[:, :R].contiguous()
 
 
+# ---- missing data: the stored entries only ------------------------------------------------------------------------------------
+def _masked_call(T: SparseTarget, side: str, owner: Tensor, panel: Tensor, beta: float, step=None, _fill=None, _ws=None):
+    """``nmfmu_sp_masked_terms`` (``step`` None: returns (num, den), fp32 ``[owner rows, r_pad]``) or ``nmfmu_sp_masked_step``
+    (``step`` = (l1, l2, gamma): ``owner`` updated in place).  ``owner`` / ``panel``: contiguous fp32 ``[rows, R]``.  Enqueued
+    only.  ``_fill``: tests pre-fill the outputs and the workspace with it."""
+    lib = _capi.load()
+    dev = owner.device
+    rows, R = owner.shape
+    r_pad = lib.nmfmu_pad_rank(R)
+    (ptr, idx, vals), seg, multi, n_ws = T.side(side)
+    assert rows == ptr.numel() - 1 and panel.shape[1] == R
+    n_float = lib.nmfmu_sp_masked_ws(n_ws, r_pad)
+    ws = _ws if _ws is not None else (torch.empty(n_float, dtype=torch.float32, device=dev) if n_float else None)
+    if _fill is not None and ws is not None:
+        ws.fill_(_fill)
+    head = (seg.data_ptr(), seg.shape[0], multi.data_ptr() if multi.shape[0] else None, multi.shape[0], T.entries(idx),
+            T.entries(vals), owner.data_ptr(), panel.data_ptr(), R, beta)
+    wsp = ws.data_ptr() if ws is not None else None
+    if step is not None:
+        l1, l2, gamma = step
+        _capi.check(lib.nmfmu_sp_masked_step(*head, l1, l2, gamma, wsp, r_pad, _stream()), 'nmfmu_sp_masked_step')
+        return None
+    num = torch.empty(rows, r_pad, dtype=torch.float32, device=dev)
+    den = torch.empty(rows, r_pad, dtype=torch.float32, device=dev)
+    if _fill is not None:
+        num.fill_(_fill)
+        den.fill_(_fill)
+    _capi.check(lib.nmfmu_sp_masked_terms(*head, wsp, num.data_ptr(), den.data_ptr(), r_pad, _stream()),
+                'nmfmu_sp_masked_terms')
+    return num, den
+
+
+def _masked_loss(Hc: Tensor, Wc: Tensor, T: SparseTarget, beta: float, part=None, out=None) -> Tensor:
+    """``metrics.beta_div`` over the stored entries as a 1-element float64 device tensor.  Enqueued only (the terms of v
+    alone are cached on the target after their first use)."""
+    lib = _capi.load()
+    rowptr, colidx, vals = T.csr
+    n_seg = T.seg_h.shape[0]
+    if part is None:
+        part = torch.empty((n_seg + 3) // 4, dtype=torch.float64, device=Hc.device)
+    if out is None:
+        out = torch.empty(1, dtype=torch.float64, device=Hc.device)
+    _capi.check(lib.nmfmu_sp_masked_loss(T.seg_h.data_ptr(), n_seg, T.entries(colidx), T.entries(vals), Hc.data_ptr(),
+                                         Wc.data_ptr(), Hc.shape[1], beta, T.masked_v_term(beta), part.data_ptr(),
+                                         out.data_ptr(), _stream()), 'nmfmu_sp_masked_loss')
+    return out
+
+
+class _MaskedBetaDivFn(torch.autograd.Function):
+    """The masked loss; both gradients are up (den - num) of one ``nmfmu_sp_masked_terms`` call per wanted side."""
+
+    @staticmethod
+    def forward(ctx, H, W, T, beta):
+        ctx.save_for_backward(H, W)
+        ctx.T, ctx.beta = T, beta
+        return _masked_loss(_f32(H), _f32(W), T, beta)[0].float()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        H, W = ctx.saved_tensors
+        Hc, Wc = _f32(H), _f32(W)
+        up = g.detach().float()
+        R = H.shape[1]
+
+        def grad(side, owner, panel, like):
+            num, den = _masked_call(ctx.T, side, owner, panel, ctx.beta)
+            return (up * (den - num))[:, :R].to(like.dtype)
+        gH = grad('h', Hc, Wc, H) if ctx.needs_input_grad[0] else None
+        gW = grad('w', Wc, Hc, W) if ctx.needs_input_grad[1] else None
+        return gH, gW, None, None
+
+
 class _SparseBetaDivFn(torch.autograd.Function):
     """The value from the same launches as without autograd; both gradients from ``nmfmu_sp_div_backward``, which reads the
     0-dim incoming gradient on the device (no host sync)."""
@@ -253,12 +374,19 @@ class _SparseBetaDivFn(torch.autograd.Function):
         return gH, gW, None, None
 
 
-def sparse_beta_div(H: Tensor, W: Tensor, target, beta: float = 2) -> Tensor:
+def sparse_beta_div(H: Tensor, W: Tensor, target, beta: float = 2, *, unstored: str = 'zero') -> Tensor:
     """beta-divergence between ``H @ W.T`` and a sparse-COO ``target`` (N, C), from the stored entries only: the
     reference's ``V_norm + pos - neg``; beta in {1, 2}, rank <= 256.  ``H`` is (N, R), ``W`` (C, R).  ``target`` is a
     ``SparseTarget`` (prepared once) or a sparse tensor (prepared for this call).  Returns a 0-dim float32 device tensor,
-    differentiable with respect to ``H`` and ``W`` (first order); the target is a constant."""
-    beta = check_beta(beta)
+    differentiable with respect to ``H`` and ``W`` (first order); the target is a constant.
+
+    ``unstored='zero'`` (default) counts every unstored entry as an observed zero, like the reference.  ``unstored='missing'``
+    leaves them out: the result is the reference's ``beta_div`` between the reconstruction at the stored entries and the
+    stored values, for ANY beta (beta <= 0 needs strictly positive stored values)."""
+    if unstored not in ('zero', 'missing'):
+        raise ValueError(f"unstored must be 'zero' or 'missing', got {unstored!r}")
+    missing = unstored == 'missing'
+    beta = float(beta) if missing else check_beta(beta)
     assert isinstance(target, SparseTarget) or (isinstance(target, Tensor) and target.is_sparse), \
         'the target must be a SparseTarget or a sparse COO tensor'
     assert H.dim() == 2 and W.dim() == 2 and H.shape[1] == W.shape[1], 'H must be (N, R) and W (C, R)'
@@ -273,6 +401,13 @@ def sparse_beta_div(H: Tensor, W: Tensor, target, beta: float = 2) -> Tensor:
     assert H.device == W.device == target.device, 'H, W and the target must live on the same device'
     if not (H.dtype.is_floating_point and W.dtype.is_floating_point):
         raise NotImplementedError(f'factors must be floating point; got H {H.dtype}, W {W.dtype}')
+    if missing:
+        if beta <= 0 and target.has_zero:
+            raise ValueError('When beta <= 0 and V contains zeros, the training process may diverge. '
+                             'Please add small values to V, or use a positive beta value.')
+        if torch.is_grad_enabled() and (H.requires_grad or W.requires_grad):
+            return _MaskedBetaDivFn.apply(H, W, target, beta)
+        return _masked_loss(_f32(H), _f32(W), target, beta)[0].float()
     if torch.is_grad_enabled() and (H.requires_grad or W.requires_grad):
         return _SparseBetaDivFn.apply(H, W, target, beta)
     return _forward(_f32(H), _f32(W), target, beta, want_s=False)[0]

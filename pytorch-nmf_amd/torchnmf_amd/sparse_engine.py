@@ -16,6 +16,9 @@ the dense numerator / denominator terms restricted to those entries, so the fact
                the O(R^2) terms from the column sums / Gram matrices
 
 beta <= 0 is rejected like in the reference (nmf.py:332-336: a sparse target always contains zeros).
+
+``MaskedMU`` is the engine of ``fit(..., unstored='missing')``: the unstored entries are unknown, not zero, and numerator AND
+denominator run over the stored entries only (nmfmu_sp_masked_step) -- O(nnz R) for every beta, beta <= 0 included.
 """
 from __future__ import annotations
 
@@ -24,6 +27,7 @@ import ctypes as C
 import torch
 
 from . import _capi
+from . import sparse_autograd as SA
 from .engine import DEFAULT_BACKEND_FACTORY, FactorBuf, StepBuf, _ptr, mu_gamma
 
 
@@ -180,3 +184,50 @@ class SparseMU:
         """V_norm + pos - neg (nmf.py:357, 397).  One host sync."""
         self._launch_neg()
         return self.v_norm + self._pos() - float(self.loss_out.item())
+
+
+class MaskedMU:
+    """Same interface as ``SparseMU`` for a sparse target read as MISSING DATA: only its stored entries are fitted.
+
+    ``V``: a sparse-COO tensor or a ready-made ``sparse_autograd.SparseTarget``.  ``W`` (C, R) / ``H`` (N, R): the contiguous
+    fp32 masters, updated in place -- no operand images, no column sums, exact fp32 arithmetic.  One half-step is one
+    ``nmfmu_sp_masked_step`` call: the gather kernel applies nmf.py:78-92 to the rows it finishes."""
+    precision_name = 'fp32'
+
+    def __init__(self, V, W, H, beta, l1=0.0, l2=0.0, update_W=True, update_H=True, chunk=None):
+        self.beta = float(beta)
+        T = V if isinstance(V, SA.SparseTarget) else SA.SparseTarget(V, **({} if chunk is None else {'chunk': chunk}))
+        N, Cc = T.shape
+        R = W.shape[1]
+        assert W.shape == (Cc, R) and H.shape == (N, R)
+        if R > SA.MAX_RANK:
+            raise NotImplementedError(f"unstored='missing': rank {R} > {SA.MAX_RANK}, the limit of the sparse kernels")
+        for f in (W, H):
+            assert f.dtype == torch.float32 and f.is_contiguous() and f.device == T.device, \
+                'MaskedMU works on contiguous fp32 masters on the target\'s device'
+        self.T, self.W, self.H = T, W, H
+        self.update_W, self.update_H = bool(update_W), bool(update_H)
+        self.reg = (float(l1), float(l2), mu_gamma(self.beta))
+        self.bad = bool((~(T.vals >= 0)).any().item()) if T.nnz else False      # nmf.py:329-330
+        self.has_zero = T.has_zero                                             # stored zeros only: unstored is unknown
+        lib, dev = _capi.load(), T.device
+        r_pad = lib.nmfmu_pad_rank(R)
+        n_ws = lib.nmfmu_sp_masked_ws(max(T.n_ws_h, T.n_ws_w), r_pad)
+        self.ws = torch.empty(n_ws, dtype=torch.float32, device=dev) if n_ws else None
+        self.loss_part = torch.empty((T.seg_h.shape[0] + 3) // 4, dtype=torch.float64, device=dev)
+        self.loss_out = torch.zeros(1, dtype=torch.float64, device=dev)
+
+    def target_flags(self):
+        return self.bad, self.has_zero
+
+    def w_step(self):
+        if self.update_W:
+            SA._masked_call(self.T, 'w', self.W, self.H, self.beta, step=self.reg, _ws=self.ws)
+
+    def h_step(self):
+        if self.update_H:
+            SA._masked_call(self.T, 'h', self.H, self.W, self.beta, step=self.reg, _ws=self.ws)
+
+    def divergence(self) -> float:
+        """metrics.beta_div over the stored entries.  One host sync."""
+        return float(SA._masked_loss(self.H, self.W, self.T, self.beta, self.loss_part, self.loss_out).item())
