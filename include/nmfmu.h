@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define NMFMU_ABI_VERSION 9 /* 2: nmfmu_gemm_desc grew the implicit-operand fields; trainer / convnd / tables entries;
+#define NMFMU_ABI_VERSION 10 /* 2: nmfmu_gemm_desc grew the implicit-operand fields; trainer / convnd / tables entries;
                                3: nmfmu_gemm_desc.tile_rows, NMFMU_EPI_FOLD, NMFMU_PREC_F16;
                                4: NMFMU_PREC_F16 for every beta and padded rank 256 (four-wave kernel); nmfmu_mu_step_parts /
                                   nmfmu_parts_supported / nmfmu_gemm_tile256_supported removed (measured neutral / not faster);
@@ -60,7 +60,11 @@ extern "C" {
                                   nmfmu_conv_plca_backward_ws (torch.autograd through PLCA / SIPLCA / SIPLCA2 / SIPLCA3.forward:
                                   the two products above, finished with the latent vector Z);
                                   nmfmu_sp_masked_terms / nmfmu_sp_masked_step / nmfmu_sp_masked_loss / nmfmu_sp_masked_ws
-                                  (missing-data NMF: sparse targets fitted over their stored entries only, every beta) */
+                                  (missing-data NMF: sparse targets fitted over their stored entries only, every beta);
+                               10: nmfmu_plca_normalize / nmfmu_plca_z / nmfmu_plca3 take alpha as double (an argument changed its
+                                  type: not additive).  The Dirichlet prior adds fp32(alpha - 1) with the subtraction in double,
+                                  as the reference's in-place add does; fp32(alpha) - 1.f was off by 4.7e-5 relative at
+                                  alpha = 1.001 */
 
 #define NMFMU_OK 0
 #define NMFMU_ERR_UNSUPPORTED (-2) /* rank / precision / beta combination not built */
@@ -782,17 +786,19 @@ int nmfmu_sp_masked_loss(const int32_t* seg, int n_seg, const int32_t* colidx, c
  * Z-scaled factor as p1 (reconstruction) and of the unscaled factor as p2.  part: nmfmu_plca_part_bytes() of scratch.
  *   nmfmu_plca_em        f *= relu(num * z_old) (skipped when update == 0); colsum_out = column sums of the result;
  *                        zgrad_out (may be NULL) = sum_rows f_old * num
- *   nmfmu_plca_normalize f /= divider[r]; when alpha != 1: f += alpha - 1, clamped below at eps; colsum_out = column sums
+ *   nmfmu_plca_normalize f /= divider[r]; when alpha != 1: f += (float)(alpha - 1.0), clamped below at eps; colsum_out =
+ *                        column sums.  alpha is a double so that the constant is the reference's: the subtraction in double,
+ *                        one rounding to fp32 (the same in nmfmu_plca_z and nmfmu_plca3)
  *   nmfmu_plca_scale     f /= colsum[r] */
 size_t nmfmu_plca_part_bytes(int rows, int r_pad);
 int nmfmu_plca_em(float* f, int rows, int rank, int r_pad, const float* num, int nslab, int rows_pad, const float* z_old,
                   int update, float* part, float* colsum_out, float* zgrad_out, void* stream);
-int nmfmu_plca_normalize(float* f, int rows, int rank, int r_pad, const float* divider, float alpha, float* part,
+int nmfmu_plca_normalize(float* f, int rows, int rank, int r_pad, const float* divider, double alpha, float* part,
                          float* colsum_out, void* stream);
 int nmfmu_plca_scale(float* f, int rows, int rank, const float* colsum, void* stream);
 /* plca.py:253-260 in one launch: prior[r] = z[r] * relu(zgrad[r]); z <- prior (+ alpha - 1, clamped below at eps when
  * alpha != 1), then z /= sum(z).  rank <= 256. */
-int nmfmu_plca_z(float* z, const float* zgrad, int rank, float alpha, float* prior, void* stream);
+int nmfmu_plca_z(float* z, const float* zgrad, int rank, double alpha, float* prior, void* stream);
 
 /* ---- shift-invariant PLCA (SIPLCA / SIPLCA2 / SIPLCA3, plca.py:376-606) on the NMFD GEMM path ----------------------
  * Same EM update as PLCA with W (C, R, *T), H (B, R, *Lh): factors are addressed [outer][rank][inner], the unscaled
@@ -841,7 +847,7 @@ int nmfmu_conv_rows_fold(float* out, int batch, int rank, int lh_outer, int lh_l
 int nmfmu_slab_sum(float* slabs, int64_t slab_elems, int nslab, void* stream);
 size_t nmfmu_plca3_part_bytes(int rank);
 int nmfmu_plca3(int mode, float* f, int outer, int rank, int inner, const float* num, int64_t num_pitch, const float* vec,
-                float alpha, int update, float* part, float* colsum_out, float* zgrad_out, void* stream);
+                double alpha, int update, float* part, float* colsum_out, float* zgrad_out, void* stream);
 
 /* ---- the collective of the column-sharded path ----------------------------------------------
  * One process (or host thread) per GPU, or one process driving several: the H half-step sums ONE packed fp32 buffer

@@ -4,9 +4,12 @@
 // with a split panel (first GEMM reads the image of the Z-scaled factor, second GEMM the unscaled one).  What is left
 // is O((N + C) R) per factor, the three small kernels here:
 //   plca_em        f *= relu(num * z_old)          + column sums of the result + Z.grad partials  sum_rows f_old * num
-//   plca_normalize f /= divider ; Dirichlet prior: f += alpha - 1, clamp below at eps ; column sums of the result
+//   plca_normalize f /= divider ; Dirichlet prior: f += fp32(alpha - 1), clamp below at eps ; column sums of the result
 //   plca_scale     f /= colsum                     (renormalisation after a prior)
 // Column sums are two-stage and order-fixed (deterministic), like everywhere else in this library.
+// The prior's constant is formed on the host as the reference forms it (plca.py:260, 274, 288: ``alpha - 1`` in double, rounded
+// to fp32 by the in-place add): the kernels take that ``shift`` and a flag ``prior`` = (alpha != 1), never alpha itself --
+// fp32(alpha) - 1.f is another number (4.7e-5 relative at alpha = 1.001).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -22,7 +25,7 @@ constexpr int kPlcaRows = 32;   // factor rows per workgroup (128 measured slowe
 template <int MODE>   // 0: em, 1: normalize
 __global__ void __launch_bounds__(256) plca_kernel(float* __restrict__ f, int rows, int rank, int r_pad,
                                                    const float* __restrict__ num, int nslab, size_t plane,
-                                                   const float* __restrict__ vec, float alpha, int update,
+                                                   const float* __restrict__ vec, float shift, int prior, int update,
                                                    float* __restrict__ cs_part, float* __restrict__ zg_part) {
   __shared__ float red[2][256];
   const int tid = threadIdx.x, r = tid % r_pad, g = tid / r_pad, groups = 256 / r_pad;
@@ -43,8 +46,8 @@ __global__ void __launch_bounds__(256) plca_kernel(float* __restrict__ f, int ro
         x *= fmaxf(n * v, 0.f);                        // f *= relu(f.grad), f.grad = num * z_old  (plca.py:263, 277)
       } else {
         x /= v;                                        // plca.py:270, 284
-        if (alpha != 1.f) {
-          x += alpha - 1.f;                            // plca.py:272-274, 286-288
+        if (prior) {
+          x += shift;                                  // plca.py:272-274, 286-288
           x = x > kEps ? x : kEps;                     // F.threshold(x, eps, eps)
         }
       }
@@ -68,18 +71,18 @@ __global__ void __launch_bounds__(256) plca_scale_kernel(float* __restrict__ f, 
 }
 
 // The latent update of plca.py:253-260 in one launch (round 4; it was a dozen R-element torch ops per EM iteration):
-// prior[r] = z[r] * relu(zgrad[r]) (what the factors' normalisation divides by); z <- prior (+ Dirichlet prior: + alpha - 1,
+// prior[r] = z[r] * relu(zgrad[r]) (what the factors' normalisation divides by); z <- prior (+ Dirichlet prior: + shift,
 // clamped below at eps); z /= sum(z).  One workgroup, rank <= 256, fixed-order sum.
 __global__ void __launch_bounds__(256) plca_z_kernel(float* __restrict__ z, const float* __restrict__ zgrad, int rank,
-                                                     float alpha, float* __restrict__ prior) {
+                                                     float shift, int has_prior, float* __restrict__ prior) {
   __shared__ float red[256];
   const int r = threadIdx.x;
   float z1 = 0.f;
   if (r < rank) {
     z1 = z[r] * fmaxf(zgrad[r], 0.f);
     prior[r] = z1;
-    if (alpha != 1.f) {
-      z1 += alpha - 1.f;
+    if (has_prior) {
+      z1 += shift;
       z1 = z1 > kEps ? z1 : kEps;
     }
   }
@@ -104,7 +107,7 @@ constexpr int kPlca3Chunks = 64;
 template <int MODE>   // 0: em, 1: normalize, 2: scale
 __global__ void __launch_bounds__(256) plca3_kernel(float* __restrict__ f, int outer, int R, int inner,
                                                     const float* __restrict__ num, int64_t num_pitch,
-                                                    const float* __restrict__ vec, float alpha, int update,
+                                                    const float* __restrict__ vec, float shift, int prior, int update,
                                                     float* __restrict__ part) {
   __shared__ float red[2][256];
   const int r = blockIdx.x, ch = blockIdx.y, tid = threadIdx.x;
@@ -122,8 +125,8 @@ __global__ void __launch_bounds__(256) plca3_kernel(float* __restrict__ f, int o
       x *= fmaxf(nv * v, 0.f);
     } else if constexpr (MODE == 1) {
       x /= v;
-      if (alpha != 1.f) {
-        x += alpha - 1.f;
+      if (prior) {
+        x += shift;
         x = x > kEps ? x : kEps;
       }
     } else {
@@ -162,6 +165,7 @@ using namespace nmfmu;
 namespace {
 inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
 inline int nblk_of(int rows) { return (rows + kPlcaRows - 1) / kPlcaRows; }
+inline float prior_shift(double alpha) { return (float)(alpha - 1.0); }   // the subtraction in double, ONE rounding to fp32
 }  // namespace
 
 extern "C" {
@@ -177,18 +181,18 @@ int nmfmu_plca_em(float* f, int rows, int rank, int r_pad, const float* num, int
   const int nb = nblk_of(rows);
   float* zg_part = zgrad_out ? part + (size_t)nb * r_pad : nullptr;
   hipLaunchKernelGGL(plca_kernel<0>, dim3(nb), dim3(256), 0, S(stream), f, rows, rank, r_pad, num, nslab,
-                     (size_t)rows_pad * r_pad, z_old, 1.f, update, part, zg_part);
+                     (size_t)rows_pad * r_pad, z_old, 0.f, 0, update, part, zg_part);
   int e = launch_colsum_finalize(part, nb, r_pad, colsum_out, S(stream));   // two-stage, order-fixed (nmfmu_aux.hip)
   if (!e && zgrad_out) e = launch_colsum_finalize(zg_part, nb, r_pad, zgrad_out, S(stream));
   return e;
 }
 
-int nmfmu_plca_normalize(float* f, int rows, int rank, int r_pad, const float* divider, float alpha, float* part,
+int nmfmu_plca_normalize(float* f, int rows, int rank, int r_pad, const float* divider, double alpha, float* part,
                          float* colsum_out, void* stream) {
   if (!f || !divider || !part || !colsum_out || rows <= 0 || rank <= 0 || r_pad != nmfmu_pad_rank(rank)) return NMFMU_ERR_ARG;
   const int nb = nblk_of(rows);
   hipLaunchKernelGGL(plca_kernel<1>, dim3(nb), dim3(256), 0, S(stream), f, rows, rank, r_pad, nullptr, 0, (size_t)0, divider,
-                     alpha, 1, part, nullptr);
+                     prior_shift(alpha), (int)(alpha != 1.0), 1, part, nullptr);
   return launch_colsum_finalize(part, nb, r_pad, colsum_out, S(stream));
 }
 
@@ -200,9 +204,9 @@ int nmfmu_plca_scale(float* f, int rows, int rank, const float* colsum, void* st
   return (int)hipGetLastError();
 }
 
-int nmfmu_plca_z(float* z, const float* zgrad, int rank, float alpha, float* prior, void* stream) {
+int nmfmu_plca_z(float* z, const float* zgrad, int rank, double alpha, float* prior, void* stream) {
   if (!z || !zgrad || !prior || rank <= 0 || rank > 256) return NMFMU_ERR_ARG;
-  hipLaunchKernelGGL(plca_z_kernel, dim3(1), dim3(256), 0, S(stream), z, zgrad, rank, alpha, prior);
+  hipLaunchKernelGGL(plca_z_kernel, dim3(1), dim3(256), 0, S(stream), z, zgrad, rank, prior_shift(alpha), (int)(alpha != 1.0), prior);
   return (int)hipGetLastError();
 }
 
@@ -210,17 +214,18 @@ size_t nmfmu_plca3_part_bytes(int rank) { return rank > 0 ? (size_t)rank * kPlca
 
 /* mode 0: em (num, z_old), 1: normalize (divider, alpha), 2: scale (colsum) -- see nmfmu_plca_* for the semantics */
 int nmfmu_plca3(int mode, float* f, int outer, int rank, int inner, const float* num, int64_t num_pitch, const float* vec,
-                float alpha, int update, float* part, float* colsum_out, float* zgrad_out, void* stream) {
+                double alpha, int update, float* part, float* colsum_out, float* zgrad_out, void* stream) {
   if (!f || !vec || outer <= 0 || rank <= 0 || inner <= 0 || mode < 0 || mode > 2) return NMFMU_ERR_ARG;
   if (mode == 0 && (!num || num_pitch < (int64_t)rank * inner)) return NMFMU_ERR_ARG;
   if (mode != 2 && (!part || !colsum_out)) return NMFMU_ERR_ARG;
   const dim3 grid(rank, kPlca3Chunks);
   if (mode == 0)
-    hipLaunchKernelGGL(plca3_kernel<0>, grid, dim3(256), 0, S(stream), f, outer, rank, inner, num, num_pitch, vec, 1.f, update, part);
+    hipLaunchKernelGGL(plca3_kernel<0>, grid, dim3(256), 0, S(stream), f, outer, rank, inner, num, num_pitch, vec, 0.f, 0, update, part);
   else if (mode == 1)
-    hipLaunchKernelGGL(plca3_kernel<1>, grid, dim3(256), 0, S(stream), f, outer, rank, inner, nullptr, (int64_t)0, vec, alpha, 1, part);
+    hipLaunchKernelGGL(plca3_kernel<1>, grid, dim3(256), 0, S(stream), f, outer, rank, inner, nullptr, (int64_t)0, vec, prior_shift(alpha),
+                       (int)(alpha != 1.0), 1, part);
   else
-    hipLaunchKernelGGL(plca3_kernel<2>, grid, dim3(256), 0, S(stream), f, outer, rank, inner, nullptr, (int64_t)0, vec, 1.f, 1,
+    hipLaunchKernelGGL(plca3_kernel<2>, grid, dim3(256), 0, S(stream), f, outer, rank, inner, nullptr, (int64_t)0, vec, 0.f, 0, 1,
                        (float*)nullptr);
   if (mode != 2)
     hipLaunchKernelGGL(plca3_final_kernel, dim3((rank + 63) / 64), dim3(64), 0, S(stream), part, rank, colsum_out,

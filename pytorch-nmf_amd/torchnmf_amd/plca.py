@@ -190,9 +190,9 @@ class _PlcaEM:
             precision = 'bf16x3' if self.be.supported(self.r_pad, _capi.PREC_BF16X3) else 'bf16'
         if precision not in _capi.PRECISIONS:
             raise ValueError(f"precision must be one of {sorted(_capi.PRECISIONS)} or 'auto', got {precision!r}")
-        if precision in ('f16x', 'f16'):
-            # (ADVICE r4 / r5) the target is normalised to sum 1 here and the factors are probability tables: both sit in
-            # fp16's subnormals, so either fp16 mode would flush them (and 'f16x' has no split-panel instance at all)
+        if precision in ('f16x', 'f16', 'f16r'):
+            # (ADVICE r4 / r5 / r6) the target is normalised to sum 1 here and the factors are probability tables: both sit in
+            # fp16's subnormals, so every fp16-operand mode would flush them (and 'f16x' / 'f16r' have no split-panel instance)
             raise NotImplementedError(f"precision {precision!r} is not available for PLCA: the normalised target and factors "
                                       "sit below fp16's range -- use 'bf16x3' (the default) or 'bf16'")
         self.prec = _capi.PRECISIONS[precision]

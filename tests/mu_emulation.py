@@ -199,7 +199,7 @@ AMBIGUITY = 2e-6
 
 
 def half_step(X, A, B, beta: float, precision: str, *, M=None, K=None, cs_owner=None, cs_panel=None, rounding=True,
-              A_img=None, B_img=None, ratio_round=None, x_stored=None):
+              A_img=None, B_img=None, ratio_round=None, x_stored=None, B2=None, B2_img=None):
     """Numerator and denominator of one half-step, float64, [rows of A] x rank.
 
     X: [m, k] fp32 target rows (V or V^T); A: [m, R] owner rows; B: [k, R] panel.  ``A_img`` / ``B_img`` = (hi, lo or None)
@@ -208,7 +208,9 @@ def half_step(X, A, B, beta: float, precision: str, *, M=None, K=None, cs_owner=
     (ki).  rounding=False: every operand exact (the plain float64 algorithm of mu_oracle).  ``ratio_round(G, split)``:
     replaces the Gn / Gp rounding (seeded-fault tests).  ``x_stored``:
     the target as the kernel holds it, used instead of ``stored_target(X, precision)`` (the convolutive engine keeps fp32
-    targets in every precision: tests/conv_emulation.py).
+    targets in every precision: tests/conv_emulation.py).  ``B2`` / ``B2_img``: the contraction panel where it is another
+    matrix than the reconstruction panel (the split panel of PLCA's EM step, kModeMU2: S = A B^T + eps from ``B`` -- the
+    Z-scaled factor -- and num = Gn B2 with the unscaled one); default: ``B`` / ``B_img`` itself, nothing changes.
 
     Returns a dict: num, den (None at beta == 1), ki, and num_amb / den_amb -- per element, the largest difference that
     the ambiguous terms (AMBIGUITY) can make."""
@@ -220,8 +222,10 @@ def half_step(X, A, B, beta: float, precision: str, *, M=None, K=None, cs_owner=
         Ah, Al = A_img if A_img is not None else factor_image(A, precision)
         Bh, Bl = B_img if B_img is not None else factor_image(B, precision)
         x = stored_target(X, precision) if x_stored is None else np.asarray(x_stored, dtype=np.float64)
+        Ch, Cl = B2_img if B2_img is not None else ((Bh, Bl) if B2 is None else factor_image(B2, precision))
     else:
         Ah, Al, Bh, Bl, x = (np.asarray(A, np.float64), None, np.asarray(B, np.float64), None, X)
+        Ch, Cl = (Bh if B2 is None else np.asarray(B2, np.float64)), None
     S = _gemm([Ah] if Al is None else [Ah, Al], Bh.T, None if Bl is None else Bl.T)
     if kind != 'euc':
         S = S + EPS
@@ -230,15 +234,15 @@ def half_step(X, A, B, beta: float, precision: str, *, M=None, K=None, cs_owner=
     unsc = 2.0 ** -ki
     out = {'ki': ki, 'num_amb': 0.0, 'den_amb': 0.0, 'den': None}
     if not rounding:
-        out['num'] = gn @ Bh
-        out['den'] = None if gp is None else gp @ Bh
+        out['num'] = gn @ Ch
+        out['den'] = None if gp is None else gp @ Ch
         return out
     rr = ratio_round or (lambda G, split: rounded_terms(G, precision, split))
-    Babs = np.abs(Bh)
+    Babs = np.abs(Ch)
 
     def contract(G, split, key):
         ops = rr(G, split)
-        res = _gemm(ops, Bh, Bl) * unsc
+        res = _gemm(ops, Ch, Cl) * unsc
         if not split:       # (a hi + lo pair holds the term to 2^-16 whichever way hi went)
             flip = np.abs(round_op(G * (1 + AMBIGUITY), precision) - round_op(G * (1 - AMBIGUITY), precision))
             if flip.any():
@@ -246,7 +250,7 @@ def half_step(X, A, B, beta: float, precision: str, *, M=None, K=None, cs_owner=
         out[key] = res
 
     if kind == 'euc' and precision in ('bf16', 'f16'):
-        out['num'] = x @ Bh                                   # the stored word is the operand (nmfmu_fused.h:690)
+        out['num'] = x @ Ch                                   # the stored word is the operand (nmfmu_fused.h:690)
     else:
         contract(gn, precision == 'bf16x3' or (precision == 'f16x' and kind == 'euc'), 'num')
     if gp is not None:

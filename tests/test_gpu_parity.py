@@ -2064,6 +2064,8 @@ def test_plca_fit_g13_tensor_alphas_golden(dev):
         m.fit(t(g['V']).to(dev), max_iter=1, precision='f16x')
     with pytest.raises(NotImplementedError, match="below fp16's range"):      # ('f16' as well)
         m.fit(t(g['V']).to(dev), max_iter=1, precision='f16')
+    with pytest.raises(NotImplementedError, match="'f16r' is not available for PLCA"):   # (no split-panel instance)
+        m.fit(t(g['V']).to(dev), max_iter=1, precision='f16r')
     #  the hyper-parameter of a FROZEN factor is never evaluated by the reference: a multi-element tensor passes there
     m2 = PLCA(W=t(g['W0']), H=t(g['H0']), Z=t(g['Z0']), trainable_W=False).to(dev)
     m2.fit(t(g['V']).to(dev), max_iter=2, W_alpha=torch.ones(3))

@@ -119,8 +119,8 @@ def test_library_exports_every_declared_symbol():
 
 def test_static_queries():
     lib = _capi.load()
-    assert lib.nmfmu_abi_version() == _capi.ABI_VERSION == 9
-    assert lib.nmfmu_abi_check(9) == 0 and lib.nmfmu_abi_check(8) == _capi.ERR_ARG     # load-time guard of foreign bindings
+    assert lib.nmfmu_abi_version() == _capi.ABI_VERSION == 10    # 10: nmfmu_plca_normalize / _z / nmfmu_plca3 take alpha as double
+    assert lib.nmfmu_abi_check(10) == 0 and lib.nmfmu_abi_check(9) == _capi.ERR_ARG     # load-time guard of foreign bindings
     assert [lib.nmfmu_pad_rows(r) for r in (1, 256, 257, 4096)] == [256, 256, 512, 4096]
     assert [lib.nmfmu_pad_rank(r) for r in (1, 32, 33, 88, 128, 129, 256)] == [32, 32, 64, 128, 128, 256, 256]
     assert lib.nmfmu_pad_rank(257) == _capi.ERR_UNSUPPORTED
@@ -712,8 +712,13 @@ def test_plca_tensor_alpha_contract_matches_the_reference():
 
 def test_plca_rejects_f16x_with_a_clear_message():
     """'f16x' passed PLCA's constructor checks and failed inside the first EM step with a misleading rank
-    message.  The precision is validated where the engine is built -- visible here without a GPU through the message."""
+    message.  The precision is validated where the engine is built -- visible here without a GPU through the message.
+    ADVICE r6: 'f16r' has no split-panel instance either and failed the same way; the same guard names all three."""
     import inspect
     from torchnmf_amd import plca
     src = inspect.getsource(plca._PlcaEM.__init__)
-    assert "precision in ('f16x', 'f16')" in src and 'NotImplementedError' in src
+    assert "precision in ('f16x', 'f16'" in src and 'NotImplementedError' in src
+    guard = re.search(r"if precision in \(([^)]*)\):\s*\n(?:\s*#.*\n)*\s*raise NotImplementedError", src)
+    assert guard and {p.strip(" '") for p in guard.group(1).split(',')} == {'f16x', 'f16', 'f16r'}
+    # the three fp16-operand modes are exactly the ones refused: every other precision name reaches the engine
+    assert set(_capi.PRECISIONS) - {'f16x', 'f16', 'f16r'} == {'bf16', 'bf16x3'}
