@@ -11,11 +11,16 @@
 // nmfmu_rowmat below).  The generic branch's positive term runs over EVERY entry of the reconstruction (nmf.py:628-636):
 // its denominator is a dense pass of the fused kernel without a target (nmfmu_den_partial, nmfmu_capi.hip), not in this
 // file.  nmfmu_sp_loss_neg is the O(nnz) term of the tracked loss for all three.
+//
+// The row load, kSpU, the workgroup's double partial and the RL dispatch come from nmfmu_sparse_common.h, which the segment
+// kernels (nmfmu_sparse_autograd.hip, nmfmu_sparse_masked.hip) share; sp_reduce_kernel, which all three files launch, is
+// defined here.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/nmfmu.h"
 #include "nmfmu_fused.h"
+#include "nmfmu_sparse_common.h"
 
 namespace nmfmu {
 
@@ -39,6 +44,8 @@ __global__ void __launch_bounds__(256) sp_partial_kernel(const int32_t* __restri
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   float a[RL], acc[RL];
+  // (load_row of nmfmu_sparse_common.h, written out: through the helper this kernel's prologue is allocated differently --
+  // 334 against 336 instructions at RL 1 -- and its device code is held to the instruction, it is the one bench.py times)
 #pragma unroll
   for (int q = 0; q < RL; ++q) {
     const int r = lane + 64 * q;
@@ -46,9 +53,8 @@ __global__ void __launch_bounds__(256) sp_partial_kernel(const int32_t* __restri
     acc[q] = 0.f;
   }
   const int p0 = rowptr[row], p1 = rowptr[row + 1];
-  // U stored entries per trip: their index / value / panel-row loads are independent, so U gathers are in flight per
-  // wave instead of one (the loop is otherwise a chain of two dependent loads per entry)
-  constexpr int U = 4;
+  // U stored entries per trip (the loop is otherwise a chain of two dependent loads per entry)
+  constexpr int U = kSpU;
   for (int p = p0; p < p1; p += U) {
     int col[U];
     float v[U], b[U][RL];
@@ -99,7 +105,8 @@ __global__ void __launch_bounds__(256) sp_partial_kernel(const int32_t* __restri
 }
 
 // neg term of the tracked loss: sum over stored entries of v log(s + eps) (beta == 1) or v s (beta == 2); one
-// double partial per workgroup (4 rows), summed on the host side of the ABI in a fixed order by sp_reduce_kernel.
+// double partial per workgroup (4 rows), summed on the host side of the ABI in a fixed order by sp_reduce_kernel.  Every
+// lane holds the whole row's tot (wave_sum gives each lane the same s): the waves' totals only, no lane butterfly.
 template <int RL, int KIND>
 __global__ void __launch_bounds__(256) sp_loss_kernel(const int32_t* __restrict__ rowptr,
                                                       const int32_t* __restrict__ colidx,
@@ -108,16 +115,12 @@ __global__ void __launch_bounds__(256) sp_loss_kernel(const int32_t* __restrict_
                                                       const float* __restrict__ panel, int rank,
                                                       double* __restrict__ part, float beta) {
   __shared__ double red[4];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int row = blockIdx.x * 4 + w;
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   double tot = 0.0;
   if (row < rows) {
     float a[RL];
-#pragma unroll
-    for (int q = 0; q < RL; ++q) {
-      const int r = lane + 64 * q;
-      a[q] = r < rank ? owner[(size_t)row * rank + r] : 0.f;
-    }
+    load_row<RL>(a, owner, row, rank, lane);
     for (int p = rowptr[row]; p < rowptr[row + 1]; ++p) {
       const int col = colidx[p];
       float partial = 0.f;
@@ -132,12 +135,12 @@ __global__ void __launch_bounds__(256) sp_loss_kernel(const int32_t* __restrict_
                           : (double)(vals[p] * exp2f((beta - 1.f) * log2f(s + kEps)) / (beta - 1.f));   // nmf.py:636
     }
   }
-  if (lane == 0) red[w] = tot;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  store_block_total(tot, red, part);
 }
 
-__global__ void __launch_bounds__(256) sp_reduce_kernel(const double* __restrict__ part, int n, double* __restrict__ out) {
+// (declared, with its contract, in nmfmu_sparse_common.h: the three sparse files launch it)
+__global__ void __launch_bounds__(256) sp_reduce_kernel(const double* __restrict__ part, int n, double add, double mul,
+                                                        double* __restrict__ out) {
   __shared__ double red[256];
   double s = 0.0;
   for (int i = threadIdx.x; i < n; i += 256) s += part[i];
@@ -147,7 +150,7 @@ __global__ void __launch_bounds__(256) sp_reduce_kernel(const double* __restrict
     if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
     __syncthreads();
   }
-  if (threadIdx.x == 0) *out = red[0];
+  if (threadIdx.x == 0) *out = (add + red[0]) * mul;
 }
 
 // gram[a][b] = sum_rows f[row][a] f[row][b]   (rank <= 256).  Two deterministic stages: workgroup (a, chunk) sums
@@ -200,8 +203,14 @@ __global__ void __launch_bounds__(256) rowmat_kernel(const float* __restrict__ o
 using namespace nmfmu;
 
 namespace {
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
+// f(std::integral_constant<int, kKL | kEuc | kGen>): the kinds of a sparse target (beta > 0)
+template <class F>
+void for_kind3(int kind, F&& f) {
+  if (kind == NMFMU_BETA_KL) f(std::integral_constant<int, kKL>{});
+  else if (kind == NMFMU_BETA_EUC) f(std::integral_constant<int, kEuc>{});
+  else f(std::integral_constant<int, kGen>{});
 }
+}  // namespace
 
 extern "C" {
 
@@ -212,14 +221,12 @@ int nmfmu_sp_partial(const int32_t* rowptr, const int32_t* colidx, const float* 
   const int kind = nmfmu_beta_kind(beta);
   if (kind == NMFMU_BETA_IS) return NMFMU_ERR_UNSUPPORTED;   // beta == 0 is rejected for sparse targets (nmf.py:332-336)
   const dim3 grid((owner_rows + 3) / 4), block(256);
-#define L2(RLV, K)                                                                                                   \
-  hipLaunchKernelGGL((sp_partial_kernel<RLV, K>), grid, block, 0, S(stream), rowptr, colidx, vals, owner_rows, owner,  \
-                     panel, rank, num, r_pad, beta);
-#define L(RLV)                                                                         \
-  if (kind == NMFMU_BETA_KL) { L2(RLV, kKL) } else if (kind == NMFMU_BETA_EUC) { L2(RLV, kEuc) } else { L2(RLV, kGen) }
-  if (r_pad <= 64) { L(1) } else if (r_pad == 128) { L(2) } else { L(4) }
-#undef L
-#undef L2
+  for_rl(r_pad, [&](auto rl) {
+    for_kind3(kind, [&](auto k) {
+      hipLaunchKernelGGL((sp_partial_kernel<decltype(rl)::value, decltype(k)::value>), grid, block, 0, S(stream), rowptr,
+                         colidx, vals, owner_rows, owner, panel, rank, num, r_pad, beta);
+    });
+  });
   return (int)hipGetLastError();
 }
 
@@ -231,15 +238,13 @@ int nmfmu_sp_loss_neg(const int32_t* rowptr, const int32_t* colidx, const float*
   if (kind == NMFMU_BETA_IS) return NMFMU_ERR_UNSUPPORTED;
   const int nblk = (owner_rows + 3) / 4;
   const int r_pad = nmfmu_pad_rank(rank);
-#define L2(RLV, K)                                                                                                   \
-  hipLaunchKernelGGL((sp_loss_kernel<RLV, K>), dim3(nblk), dim3(256), 0, S(stream), rowptr, colidx, vals, owner_rows,  \
-                     owner, panel, rank, part, beta);
-#define L(RLV)                                                                         \
-  if (kind == NMFMU_BETA_KL) { L2(RLV, kKL) } else if (kind == NMFMU_BETA_EUC) { L2(RLV, kEuc) } else { L2(RLV, kGen) }
-  if (r_pad <= 64) { L(1) } else if (r_pad == 128) { L(2) } else { L(4) }
-#undef L
-#undef L2
-  hipLaunchKernelGGL(sp_reduce_kernel, dim3(1), dim3(256), 0, S(stream), part, nblk, out);
+  for_rl(r_pad, [&](auto rl) {
+    for_kind3(kind, [&](auto k) {
+      hipLaunchKernelGGL((sp_loss_kernel<decltype(rl)::value, decltype(k)::value>), dim3(nblk), dim3(256), 0, S(stream),
+                         rowptr, colidx, vals, owner_rows, owner, panel, rank, part, beta);
+    });
+  });
+  hipLaunchKernelGGL(sp_reduce_kernel, dim3(1), dim3(256), 0, S(stream), part, nblk, 0.0, 1.0, out);
   return (int)hipGetLastError();
 }
 

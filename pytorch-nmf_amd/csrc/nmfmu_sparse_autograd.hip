@@ -21,15 +21,18 @@
 //           is bitwise identical.  pos: a broadcast vector [rank] (beta == 1: the panel's column sums) or a plane
 //           [rows][r_pad] (beta == 2: owner @ panel^T panel, nmfmu_rowmat's output).
 // Every padded rank column of `out` and of the used part of `ws` is written.
+//
+// The segment decode, the 64-entry blocks, the entry walk of the forward, the panel-row fetch of the backward, the ws slots
+// and the double partials are the shared protocol of nmfmu_sparse_common.h; this file holds what the two divergences do
+// with an entry and with a finished row.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/nmfmu.h"
 #include "nmfmu_fused.h"
+#include "nmfmu_sparse_common.h"
 
 namespace nmfmu {
-
-constexpr int kSpU = 4;   // stored entries in flight per wave and trip (as sp_partial_kernel)
 
 template <int RL, bool KL>
 __global__ void __launch_bounds__(256) sp_div_forward_kernel(const int32_t* __restrict__ seg, int n_seg,
@@ -39,74 +42,19 @@ __global__ void __launch_bounds__(256) sp_div_forward_kernel(const int32_t* __re
                                                              const float* __restrict__ panel, int rank,
                                                              float* __restrict__ s_out, double* __restrict__ part) {
   __shared__ double red[4];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int sg = blockIdx.x * 4 + w;
+  const int lane = threadIdx.x & 63;
+  const int sg = blockIdx.x * 4 + (threadIdx.x >> 6);
   double tot = 0.0;
   if (sg < n_seg) {
-    // (wave-uniform by construction: one segment per wave)
-    const int row = __builtin_amdgcn_readfirstlane(seg[4 * sg]);
-    const int p0 = __builtin_amdgcn_readfirstlane(seg[4 * sg + 1]), p1 = __builtin_amdgcn_readfirstlane(seg[4 * sg + 2]);
+    const Seg sgm = load_seg(seg, sg);
     float a[RL];
-#pragma unroll
-    for (int q = 0; q < RL; ++q) {
-      const int r = lane + 64 * q;
-      a[q] = r < rank ? owner[(size_t)row * rank + r] : 0.f;
-    }
-    // 64 entries per block: index and value are read once, one entry per lane (coalesced), and handed to the wave entry by
-    // entry; each lane keeps the dot product of ITS entry, so the store of s, the logarithm and the double sum run once
-    // per entry instead of once per entry and lane
-    for (int base = p0; base < p1; base += 64) {
-      const int pe = base + lane;
-      const int colv = pe < p1 ? colidx[pe] : 0;
-      const float vv = pe < p1 ? vals[pe] : 0.f;
-      float sv = 1.f;
-      const int cnt = min(64, p1 - base);
-      for (int j = 0; j < cnt; j += kSpU) {
-        float sdot[kSpU];
-#pragma unroll
-        for (int u = 0; u < kSpU; ++u) {
-          const int col = j + u < cnt ? __shfl(colv, (j + u) & 63, 64) : 0;
-          sdot[u] = 0.f;
-#pragma unroll
-          for (int q = 0; q < RL; ++q) {
-            const int r = lane + 64 * q;
-            sdot[u] += r < rank ? a[q] * panel[(size_t)col * rank + r] : 0.f;
-          }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1)     // kSpU fixed-order butterflies, interleaved
-#pragma unroll
-          for (int u = 0; u < kSpU; ++u) sdot[u] += __shfl_xor(sdot[u], o, 64);
-#pragma unroll
-        for (int u = 0; u < kSpU; ++u)
-          if (lane == j + u) sv = sdot[u];
-      }
-      if (pe < p1) {
-        tot += KL ? (double)(vv * logf(sv + kEps)) : (double)(vv * sv);
-        if (s_out) s_out[pe] = sv;
-      }
-    }
+    load_row<RL>(a, owner, sgm.row, rank, lane);
+    seg_entry_dots<RL>(sgm, colidx, vals, a, panel, rank, lane, [&](int pe, float v, float sv) {
+      tot += KL ? (double)(v * logf(sv + kEps)) : (double)(v * sv);
+      if (s_out) s_out[pe] = sv;
+    });
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) tot += __shfl_xor(tot, o, 64);   // the lanes' sums, fixed order
-  if (lane == 0) red[w] = tot;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// the block partials in block order (one workgroup, strided lanes, tree): the sum is a pure function of n
-__global__ void __launch_bounds__(256) sp_div_reduce_kernel(const double* __restrict__ part, int n,
-                                                            double* __restrict__ out) {
-  __shared__ double red[256];
-  double s = 0.0;
-  for (int i = threadIdx.x; i < n; i += 256) s += part[i];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *out = red[0];
+  store_lane_totals(tot, red, part);
 }
 
 __device__ __forceinline__ float sp_div_pos(const float* __restrict__ pos, bool plane, int row, int r, int rank,
@@ -127,50 +75,38 @@ __global__ void __launch_bounds__(256) sp_div_backward_kernel(const int32_t* __r
   const int lane = threadIdx.x & 63;
   const int sg = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (sg >= n_seg) return;
-  // (wave-uniform by construction: one segment per wave)
-  const int row = __builtin_amdgcn_readfirstlane(seg[4 * sg]), slot = __builtin_amdgcn_readfirstlane(seg[4 * sg + 3]);
-  const int p0 = __builtin_amdgcn_readfirstlane(seg[4 * sg + 1]), p1 = __builtin_amdgcn_readfirstlane(seg[4 * sg + 2]);
+  const Seg sgm = load_seg(seg, sg);
+  const int p1 = sgm.p1;
   float acc[RL];
 #pragma unroll
   for (int q = 0; q < RL; ++q) acc[q] = 0.f;
-  // 64 entries per block: index, value, perm and the saved s are read once, one entry per lane (coalesced but for s behind
-  // perm), g is formed once per entry -- one divide, not 64 -- and (index, g) are handed to the wave entry by entry
-  for (int base = p0; base < p1; base += 64) {
-    const int pe = base + lane;
-    const int colv = pe < p1 ? idx[pe] : 0;
-    float gv = pe < p1 ? vals[pe] : 0.f;      // g = 0 contributes nothing (s + eps > 0)
+  // per block of 64 entries: value, perm and the saved s are read once, one entry per lane like the index (coalesced but
+  // for s behind perm), g is formed once per entry -- one divide, not 64 -- and (index, g) are handed to the wave entry by
+  // entry
+  for (int base = sgm.p0; base < p1; base += 64) {
+    const EntryBlock eb = load_block(idx, base, p1, lane);
+    float gv = eb.pe < p1 ? vals[eb.pe] : 0.f;      // g = 0 contributes nothing (s + eps > 0)
     if constexpr (KL) {
-      const float sv = pe < p1 ? s[perm ? perm[pe] : pe] : 1.f;
+      const float sv = eb.pe < p1 ? s[perm ? perm[eb.pe] : eb.pe] : 1.f;
       gv = gv / (sv + kEps);
     }
-    const int cnt = min(64, p1 - base);
-    for (int j = 0; j < cnt; j += kSpU) {
+    for (int j = 0; j < eb.cnt; j += kSpU) {
       float g[kSpU], b[kSpU][RL];
+      bool ok[kSpU];
+      fetch_group<RL>(b, ok, eb, j, panel, rank, lane);
 #pragma unroll
-      for (int u = 0; u < kSpU; ++u) {
-        const bool ok = j + u < cnt;
-        const int col = ok ? __shfl(colv, (j + u) & 63, 64) : 0;
-        g[u] = ok ? __shfl(gv, (j + u) & 63, 64) : 0.f;
-#pragma unroll
-        for (int q = 0; q < RL; ++q) {
-          const int r = lane + 64 * q;
-          b[u][q] = r < rank ? panel[(size_t)col * rank + r] : 0.f;
-        }
-      }
+      for (int u = 0; u < kSpU; ++u) g[u] = ok[u] ? __shfl(gv, (j + u) & 63, 64) : 0.f;
 #pragma unroll
       for (int u = 0; u < kSpU; ++u)         // storage order
 #pragma unroll
         for (int q = 0; q < RL; ++q) acc[q] += g[u] * b[u][q];
     }
   }
-  if (slot >= 0) {
-#pragma unroll
-    for (int q = 0; q < RL; ++q) {
-      const int r = lane + 64 * q;
-      if (r < r_pad) ws[(size_t)slot * r_pad + r] = acc[q];
-    }
+  if (sgm.slot >= 0) {
+    store_partial<1, RL>(ws, sgm.slot, 0, acc, r_pad, lane);
     return;
   }
+  const int row = sgm.row;
   const float upv = up[0];
 #pragma unroll
   for (int q = 0; q < RL; ++q) {
@@ -189,12 +125,13 @@ __global__ void __launch_bounds__(256) sp_div_finish_kernel(const int32_t* __res
   const int lane = threadIdx.x & 63;
   const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (m >= n_multi) return;
-  const int row = multi[3 * m], slot0 = multi[3 * m + 1], n = multi[3 * m + 2];
+  const Multi mu = load_multi(multi, m);
   const float upv = up[0];
   for (int r = lane; r < r_pad; r += 64) {
-    float acc = ws[(size_t)slot0 * r_pad + r];
-    for (int k = 1; k < n; ++k) acc += ws[(size_t)(slot0 + k) * r_pad + r];
-    out[(size_t)row * r_pad + r] = r < rank ? upv * (sp_div_pos(pos, pos_plane != 0, row, r, rank, r_pad) - acc) : 0.f;
+    float acc[1];
+    sum_partials<1>(acc, ws, mu, r, r_pad);
+    out[(size_t)mu.row * r_pad + r] =
+        r < rank ? upv * (sp_div_pos(pos, pos_plane != 0, mu.row, r, rank, r_pad) - acc[0]) : 0.f;
   }
 }
 
@@ -203,8 +140,13 @@ __global__ void __launch_bounds__(256) sp_div_finish_kernel(const int32_t* __res
 using namespace nmfmu;
 
 namespace {
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
+// f(std::true_type) for beta == 1, f(std::false_type) for beta == 2: the two kinds of sparse_beta_div
+template <class F>
+void for_kl(int kind, F&& f) {
+  if (kind == NMFMU_BETA_KL) f(std::true_type{});
+  else f(std::false_type{});
 }
+}  // namespace
 
 extern "C" {
 
@@ -220,16 +162,13 @@ int nmfmu_sp_div_forward(const int32_t* seg, int n_seg, const int32_t* colidx, c
   const int kind = nmfmu_beta_kind(beta);
   if (kind != NMFMU_BETA_KL && kind != NMFMU_BETA_EUC) return NMFMU_ERR_UNSUPPORTED;
   const int nblk = (n_seg + 3) / 4;
-  const int r_pad = nmfmu_pad_rank(rank);
-#define L2(RLV, K)                                                                                                    \
-  hipLaunchKernelGGL((sp_div_forward_kernel<RLV, K>), dim3(nblk), dim3(256), 0, S(stream), seg, n_seg, colidx, vals,   \
-                     owner, panel, rank, s_out, part);
-#define L(RLV) \
-  if (kind == NMFMU_BETA_KL) { L2(RLV, true) } else { L2(RLV, false) }
-  if (r_pad <= 64) { L(1) } else if (r_pad == 128) { L(2) } else { L(4) }
-#undef L
-#undef L2
-  hipLaunchKernelGGL(sp_div_reduce_kernel, dim3(1), dim3(256), 0, S(stream), part, nblk, out);
+  for_rl(nmfmu_pad_rank(rank), [&](auto rl) {
+    for_kl(kind, [&](auto kl) {
+      hipLaunchKernelGGL((sp_div_forward_kernel<decltype(rl)::value, decltype(kl)::value>), dim3(nblk), dim3(256), 0,
+                         S(stream), seg, n_seg, colidx, vals, owner, panel, rank, s_out, part);
+    });
+  });
+  hipLaunchKernelGGL(sp_reduce_kernel, dim3(1), dim3(256), 0, S(stream), part, nblk, 0.0, 1.0, out);
   return (int)hipGetLastError();
 }
 
@@ -244,14 +183,12 @@ int nmfmu_sp_div_backward(const int32_t* seg, int n_seg, const int32_t* multi, i
   if (kind != NMFMU_BETA_KL && kind != NMFMU_BETA_EUC) return NMFMU_ERR_UNSUPPORTED;
   if (kind == NMFMU_BETA_KL && !s) return NMFMU_ERR_ARG;
   const int nblk = (n_seg + 3) / 4;
-#define L2(RLV, K)                                                                                                    \
-  hipLaunchKernelGGL((sp_div_backward_kernel<RLV, K>), dim3(nblk), dim3(256), 0, S(stream), seg, n_seg, idx, vals,     \
-                     perm, s, panel, rank, pos, pos_plane, up, ws, out, r_pad);
-#define L(RLV) \
-  if (kind == NMFMU_BETA_KL) { L2(RLV, true) } else { L2(RLV, false) }
-  if (r_pad <= 64) { L(1) } else if (r_pad == 128) { L(2) } else { L(4) }
-#undef L
-#undef L2
+  for_rl(r_pad, [&](auto rl) {
+    for_kl(kind, [&](auto kl) {
+      hipLaunchKernelGGL((sp_div_backward_kernel<decltype(rl)::value, decltype(kl)::value>), dim3(nblk), dim3(256), 0,
+                         S(stream), seg, n_seg, idx, vals, perm, s, panel, rank, pos, pos_plane, up, ws, out, r_pad);
+    });
+  });
   if (n_multi > 0)
     hipLaunchKernelGGL(sp_div_finish_kernel, dim3((n_multi + 3) / 4), dim3(256), 0, S(stream), multi, n_multi, ws, rank,
                        pos, pos_plane, up, out, r_pad);

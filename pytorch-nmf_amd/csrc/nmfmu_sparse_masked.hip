@@ -5,9 +5,10 @@
 //   num[row] = sum_p g_neg(v_p, s_p) * panel[idx[p]]             g_neg / g_pos: output_neg / output_pos of the reference's
 //   den[row] = sum_p g_pos(s_p)      * panel[idx[p]]             _double_backward_update (nmf.py:61-74), beta == 1: g_pos = 1
 //
-// Work is cut into the SEGMENTS of nmfmu_sparse_autograd.hip (seg / multi lists, one wave per run of <= chunk stored entries,
-// lanes across the rank, RL rank slots per lane).  Index and value of 64 entries are read once, one per lane, and handed to
-// the wave entry by entry; kMaskU entries' panel rows are in flight per trip.  Entries accumulate in storage order.  A whole
+// Work is cut into SEGMENTS (seg / multi lists, one wave per run of <= chunk stored entries, lanes across the rank, RL rank
+// slots per lane): the shared protocol of nmfmu_sparse_common.h, which also holds the 64-entry blocks, the panel-row fetch,
+// the ws slots and the double partials.  Index and value of 64 entries are read once, one per lane, and handed to
+// the wave entry by entry; kSpU entries' panel rows are in flight per trip.  Entries accumulate in storage order.  A whole
 // row is finished by the wave that formed its terms: it stores the two planes (terms) or applies nmf.py:78-92 in place to
 // the owner's fp32 master (step) -- a row is read by its own wave only, the panel is the other factor.  A split row's
 // segments store their partial [num | den] rows to ws[slot][2 r_pad] with plain stores and the finishing kernel adds them in
@@ -21,10 +22,9 @@
 
 #include "../../include/nmfmu.h"
 #include "nmfmu_fused.h"
+#include "nmfmu_sparse_common.h"
 
 namespace nmfmu {
-
-constexpr int kMaskU = 4;   // stored entries in flight per wave and trip (as sp_partial_kernel)
 
 // (g_neg, g_pos) of one stored entry; s is the plain dot product
 template <int KIND>
@@ -79,47 +79,32 @@ __global__ void __launch_bounds__(256) sp_masked_kernel(const int32_t* __restric
   const int lane = threadIdx.x & 63;
   const int sg = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (sg >= n_seg) return;
-  // (wave-uniform by construction: one segment per wave)
-  const int row = __builtin_amdgcn_readfirstlane(seg[4 * sg]), slot = __builtin_amdgcn_readfirstlane(seg[4 * sg + 3]);
-  const int p0 = __builtin_amdgcn_readfirstlane(seg[4 * sg + 1]), p1 = __builtin_amdgcn_readfirstlane(seg[4 * sg + 2]);
+  const Seg sgm = load_seg(seg, sg);
+  const int row = sgm.row, p1 = sgm.p1;
   float a[RL], an[RL], ad[RL];      // every kind reads s: EUC through g_pos = s
+  load_row<RL>(a, owner, row, rank, lane);
 #pragma unroll
-  for (int q = 0; q < RL; ++q) {
-    const int r = lane + 64 * q;
-    a[q] = r < rank ? owner[(size_t)row * rank + r] : 0.f;
-    an[q] = ad[q] = 0.f;
-  }
-  for (int base = p0; base < p1; base += 64) {
-    const int pe = base + lane;
-    const int colv = pe < p1 ? idx[pe] : 0;
-    const float vv = pe < p1 ? vals[pe] : 0.f;
-    const int cnt = min(64, p1 - base);
-    for (int j = 0; j < cnt; j += kMaskU) {
-      float v[kMaskU], b[kMaskU][RL], sdot[kMaskU];
-      bool ok[kMaskU];
+  for (int q = 0; q < RL; ++q) an[q] = ad[q] = 0.f;
+  for (int base = sgm.p0; base < p1; base += 64) {
+    const EntryBlock eb = load_block(idx, base, p1, lane);
+    const float vv = eb.pe < p1 ? vals[eb.pe] : 0.f;
+    for (int j = 0; j < eb.cnt; j += kSpU) {
+      float v[kSpU], b[kSpU][RL], sdot[kSpU];
+      bool ok[kSpU];
+      fetch_group<RL>(b, ok, eb, j, panel, rank, lane);
 #pragma unroll
-      for (int u = 0; u < kMaskU; ++u) {
-        ok[u] = j + u < cnt;
-        const int col = ok[u] ? __shfl(colv, (j + u) & 63, 64) : 0;
+      for (int u = 0; u < kSpU; ++u) {
         v[u] = __shfl(vv, (j + u) & 63, 64);
-#pragma unroll
-        for (int q = 0; q < RL; ++q) {
-          const int r = lane + 64 * q;
-          b[u][q] = (ok[u] && r < rank) ? panel[(size_t)col * rank + r] : 0.f;
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < kMaskU; ++u) {
         sdot[u] = 0.f;
 #pragma unroll
         for (int q = 0; q < RL; ++q) sdot[u] += a[q] * b[u][q];
       }
 #pragma unroll
-      for (int o = 32; o > 0; o >>= 1)     // kMaskU fixed-order butterflies, interleaved
+      for (int o = 32; o > 0; o >>= 1)     // kSpU fixed-order butterflies, interleaved
 #pragma unroll
-        for (int u = 0; u < kMaskU; ++u) sdot[u] += __shfl_xor(sdot[u], o, 64);
+        for (int u = 0; u < kSpU; ++u) sdot[u] += __shfl_xor(sdot[u], o, 64);
 #pragma unroll
-      for (int u = 0; u < kMaskU; ++u) {   // storage order; an entry past the end adds nothing
+      for (int u = 0; u < kSpU; ++u) {   // storage order; an entry past the end adds nothing
         float gn, gp;
         masked_g<KIND>(v[u], sdot[u], beta, gn, gp);
         gn = ok[u] ? gn : 0.f, gp = ok[u] ? gp : 0.f;
@@ -131,15 +116,9 @@ __global__ void __launch_bounds__(256) sp_masked_kernel(const int32_t* __restric
       }
     }
   }
-  if (slot >= 0) {
-#pragma unroll
-    for (int q = 0; q < RL; ++q) {
-      const int r = lane + 64 * q;
-      if (r < r_pad) {
-        ws[(size_t)slot * 2 * r_pad + r] = an[q];
-        ws[(size_t)slot * 2 * r_pad + r_pad + r] = ad[q];
-      }
-    }
+  if (sgm.slot >= 0) {
+    store_partial<2, RL>(ws, sgm.slot, 0, an, r_pad, lane);
+    store_partial<2, RL>(ws, sgm.slot, 1, ad, r_pad, lane);
     return;
   }
 #pragma unroll
@@ -157,15 +136,12 @@ __global__ void __launch_bounds__(256) sp_masked_finish_kernel(const int32_t* __
   const int lane = threadIdx.x & 63;
   const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (m >= n_multi) return;
-  const int row = multi[3 * m], slot0 = multi[3 * m + 1], n = multi[3 * m + 2];
+  const Multi mu = load_multi(multi, m);
   for (int r = lane; r < r_pad; r += 64) {
-    float an = ws[(size_t)slot0 * 2 * r_pad + r], ad = ws[(size_t)slot0 * 2 * r_pad + r_pad + r];
-    for (int k = 1; k < n; ++k) {
-      an += ws[(size_t)(slot0 + k) * 2 * r_pad + r];
-      ad += ws[(size_t)(slot0 + k) * 2 * r_pad + r_pad + r];
-    }
-    const float f = (step && r < rank) ? owner[(size_t)row * rank + r] : 0.f;
-    masked_finish(step, owner, num, den, row, r, rank, r_pad, f, an, ad, ap);
+    float nd[2];      // [num | den]
+    sum_partials<2>(nd, ws, mu, r, r_pad);
+    const float f = (step && r < rank) ? owner[(size_t)mu.row * rank + r] : 0.f;
+    masked_finish(step, owner, num, den, mu.row, r, rank, r_pad, f, nd[0], nd[1], ap);
   }
 }
 
@@ -196,70 +172,17 @@ __global__ void __launch_bounds__(256) sp_masked_loss_kernel(const int32_t* __re
                                                              const float* __restrict__ panel, int rank, float beta,
                                                              double* __restrict__ part) {
   __shared__ double red[4];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int sg = blockIdx.x * 4 + w;
+  const int lane = threadIdx.x & 63;
+  const int sg = blockIdx.x * 4 + (threadIdx.x >> 6);
   double tot = 0.0;
   if (sg < n_seg) {
-    // (wave-uniform by construction: one segment per wave)
-    const int row = __builtin_amdgcn_readfirstlane(seg[4 * sg]);
-    const int p0 = __builtin_amdgcn_readfirstlane(seg[4 * sg + 1]), p1 = __builtin_amdgcn_readfirstlane(seg[4 * sg + 2]);
+    const Seg sgm = load_seg(seg, sg);
     float a[RL];
-#pragma unroll
-    for (int q = 0; q < RL; ++q) {
-      const int r = lane + 64 * q;
-      a[q] = r < rank ? owner[(size_t)row * rank + r] : 0.f;
-    }
-    // each lane keeps the dot product of ITS entry of the 64: the logarithm and the double sum run once per entry
-    for (int base = p0; base < p1; base += 64) {
-      const int pe = base + lane;
-      const int colv = pe < p1 ? colidx[pe] : 0;
-      const float vv = pe < p1 ? vals[pe] : 0.f;
-      float sv = 1.f;
-      const int cnt = min(64, p1 - base);
-      for (int j = 0; j < cnt; j += kMaskU) {
-        float sdot[kMaskU];
-#pragma unroll
-        for (int u = 0; u < kMaskU; ++u) {
-          const bool ok = j + u < cnt;
-          const int col = ok ? __shfl(colv, (j + u) & 63, 64) : 0;
-          sdot[u] = 0.f;
-#pragma unroll
-          for (int q = 0; q < RL; ++q) {
-            const int r = lane + 64 * q;
-            sdot[u] += (ok && r < rank) ? a[q] * panel[(size_t)col * rank + r] : 0.f;
-          }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1)
-#pragma unroll
-          for (int u = 0; u < kMaskU; ++u) sdot[u] += __shfl_xor(sdot[u], o, 64);
-#pragma unroll
-        for (int u = 0; u < kMaskU; ++u)
-          if (lane == j + u) sv = sdot[u];
-      }
-      if (pe < p1) tot += masked_loss_term<KIND>(vv, sv, beta);
-    }
+    load_row<RL>(a, owner, sgm.row, rank, lane);
+    seg_entry_dots<RL>(sgm, colidx, vals, a, panel, rank, lane,
+                       [&](int, float v, float sv) { tot += masked_loss_term<KIND>(v, sv, beta); });
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) tot += __shfl_xor(tot, o, 64);   // the lanes' sums, fixed order
-  if (lane == 0) red[w] = tot;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// the block partials in block order (one workgroup, strided lanes, tree): *out = (add + sum) * mul
-__global__ void __launch_bounds__(256) sp_masked_reduce_kernel(const double* __restrict__ part, int n, double add, double mul,
-                                                               double* __restrict__ out) {
-  __shared__ double red[256];
-  double s = 0.0;
-  for (int i = threadIdx.x; i < n; i += 256) s += part[i];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *out = (add + red[0]) * mul;
+  store_lane_totals(tot, red, part);
 }
 
 }  // namespace nmfmu
@@ -267,8 +190,6 @@ __global__ void __launch_bounds__(256) sp_masked_reduce_kernel(const double* __r
 using namespace nmfmu;
 
 namespace {
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
 // NMFMU_OK or the answer the three entries give before any device work
 int masked_rank_check(int rank, int r_pad, bool has_r_pad) {
   if (rank <= 0) return NMFMU_ERR_ARG;
@@ -282,19 +203,12 @@ int masked_launch(const int32_t* seg, int n_seg, const int32_t* multi, int n_mul
                   int step, MaskedApply ap, hipStream_t st) {
   const int kind = nmfmu_beta_kind(beta);
   const int nblk = (n_seg + 3) / 4;
-#define L2(RLV, K)                                                                                                       \
-  hipLaunchKernelGGL((sp_masked_kernel<RLV, K>), dim3(nblk), dim3(256), 0, st, seg, n_seg, idx, vals, owner, panel, rank, \
-                     beta, ws, num, den, r_pad, step, ap);
-#define L(RLV)                                                                           \
-  switch (kind) {                                                                        \
-    case NMFMU_BETA_KL: L2(RLV, NMFMU_BETA_KL) break;                                    \
-    case NMFMU_BETA_EUC: L2(RLV, NMFMU_BETA_EUC) break;                                  \
-    case NMFMU_BETA_IS: L2(RLV, NMFMU_BETA_IS) break;                                    \
-    default: L2(RLV, NMFMU_BETA_GEN) break;                                              \
-  }
-  if (r_pad <= 64) { L(1) } else if (r_pad == 128) { L(2) } else { L(4) }
-#undef L
-#undef L2
+  for_rl(r_pad, [&](auto rl) {
+    for_kind(kind, [&](auto k) {
+      hipLaunchKernelGGL((sp_masked_kernel<decltype(rl)::value, decltype(k)::value>), dim3(nblk), dim3(256), 0, st, seg,
+                         n_seg, idx, vals, owner, panel, rank, beta, ws, num, den, r_pad, step, ap);
+    });
+  });
   if (n_multi > 0)
     hipLaunchKernelGGL(sp_masked_finish_kernel, dim3((n_multi + 3) / 4), dim3(256), 0, st, multi, n_multi, ws, owner, num,
                        den, rank, r_pad, step, ap);
@@ -335,25 +249,17 @@ int nmfmu_sp_masked_loss(const int32_t* seg, int n_seg, const int32_t* colidx, c
   if (const int rc = masked_rank_check(rank, 0, false)) return rc;
   const int kind = nmfmu_beta_kind(beta);
   const int nblk = (n_seg + 3) / 4;
-  const int r_pad = nmfmu_pad_rank(rank);
-#define L2(RLV, K)                                                                                                      \
-  hipLaunchKernelGGL((sp_masked_loss_kernel<RLV, K>), dim3(nblk), dim3(256), 0, S(stream), seg, n_seg, colidx, vals,     \
-                     owner, panel, rank, beta, part);
-#define L(RLV)                                                                           \
-  switch (kind) {                                                                        \
-    case NMFMU_BETA_KL: L2(RLV, NMFMU_BETA_KL) break;                                    \
-    case NMFMU_BETA_EUC: L2(RLV, NMFMU_BETA_EUC) break;                                  \
-    case NMFMU_BETA_IS: L2(RLV, NMFMU_BETA_IS) break;                                    \
-    default: L2(RLV, NMFMU_BETA_GEN) break;                                              \
-  }
-  if (r_pad <= 64) { L(1) } else if (r_pad == 128) { L(2) } else { L(4) }
-#undef L
-#undef L2
+  for_rl(nmfmu_pad_rank(rank), [&](auto rl) {
+    for_kind(kind, [&](auto k) {
+      hipLaunchKernelGGL((sp_masked_loss_kernel<decltype(rl)::value, decltype(k)::value>), dim3(nblk), dim3(256), 0,
+                         S(stream), seg, n_seg, colidx, vals, owner, panel, rank, beta, part);
+    });
+  });
   // metrics.py:39 halves the sum of squares; metrics.py:96 divides by beta (beta - 1)
   double mul = 1.0;
   if (kind == NMFMU_BETA_EUC) mul = 0.5;
   if (kind == NMFMU_BETA_GEN) mul = 1.0 / ((double)beta * ((double)beta - 1.0));
-  hipLaunchKernelGGL(sp_masked_reduce_kernel, dim3(1), dim3(256), 0, S(stream), part, nblk, v_term, mul, out);
+  hipLaunchKernelGGL(sp_reduce_kernel, dim3(1), dim3(256), 0, S(stream), part, nblk, v_term, mul, out);
   return (int)hipGetLastError();
 }
 

@@ -112,11 +112,20 @@ def masked_v_term(vals: Tensor, beta: float) -> float:
 
 
 def v_norm(vals: Tensor, beta: float) -> float:
-    """nmf.py:172-181 over the stored values in float64, as ``SparseMU.__init__`` computes it."""
+    """nmf.py:172-181 over the stored values in float64 (``SparseMU`` and ``SparseTarget`` both take it from here)."""
     vd = vals.double()
     if beta == 1.0:
         return float((vd @ vd.log() - vd.sum()).item())
-    return float((vd @ vd).item() * 0.5)
+    if beta == 2.0:
+        return float((vd @ vd).item() * 0.5)
+    return float(vd.pow(beta).sum().item() / beta / (beta - 1))
+
+
+def entries(t: Tensor, spare: Tensor) -> int:
+    """Pointer to an entry array (column indices, values, perm).  A target without a stored entry has empty tensors, whose
+    pointer is null; the kernels never read past the ranges of rowptr / the segments, so any valid address -- ``spare`` --
+    serves them."""
+    return t.data_ptr() if t.numel() else spare.data_ptr()
 
 
 # ---- argument checks (run before anything touches the device) -----------------------------------------------------------------
@@ -158,7 +167,7 @@ class SparseTarget:
         self.chunk = int(chunk)
         self.seg_h, self.multi_h, self.n_ws_h = plan_worklist(self.csr[0], self.chunk)
         self.seg_w, self.multi_w, self.n_ws_w = plan_worklist(self.csc[0], self.chunk)
-        self._no_entries = torch.zeros(4, dtype=torch.float32, device=V.device)
+        self.spare = torch.zeros(4, dtype=torch.float32, device=V.device)     # see entries()
         self._v_norm = {}
         self._has_zero = None
 
@@ -188,11 +197,6 @@ class SparseTarget:
         if beta not in self._v_norm:
             self._v_norm[beta] = v_norm(self.vals, beta)
         return self._v_norm[beta]
-
-    def entries(self, t: Tensor) -> int:
-        """Pointer to an entry array; a target without a stored entry has empty tensors (null pointers), and the kernels
-        never read past the segments' ranges, so any valid address serves them."""
-        return t.data_ptr() if t.numel() else self._no_entries.data_ptr()
 
 
 def _stream() -> int:
@@ -234,9 +238,9 @@ def _forward(Hc: Tensor, Wc: Tensor, T: SparseTarget, beta: float, want_s: bool)
     s = torch.empty(max(T.nnz, 1), dtype=torch.float32, device=dev) if want_s else None
     part = torch.empty((n_seg + 3) // 4, dtype=torch.float64, device=dev)
     neg = torch.empty(1, dtype=torch.float64, device=dev)
-    _capi.check(lib.nmfmu_sp_div_forward(T.seg_h.data_ptr(), n_seg, T.entries(colidx), T.entries(vals), Hc.data_ptr(),
-                                         Wc.data_ptr(), R, beta, s.data_ptr() if want_s else None, part.data_ptr(),
-                                         neg.data_ptr(), _stream()), 'nmfmu_sp_div_forward')
+    _capi.check(lib.nmfmu_sp_div_forward(T.seg_h.data_ptr(), n_seg, entries(colidx, T.spare), entries(vals, T.spare),
+                                         Hc.data_ptr(), Wc.data_ptr(), R, beta, s.data_ptr() if want_s else None,
+                                         part.data_ptr(), neg.data_ptr(), _stream()), 'nmfmu_sp_div_forward')
     pos, small = _small_terms(lib, Hc, Wc, beta)
     return (T.v_norm(beta) + pos - neg[0]).float(), s, small
 
@@ -266,8 +270,8 @@ def _backward_side(owner: Tensor, panel: Tensor, small_panel: Tensor, T: SparseT
         if ws is not None:
             ws.fill_(_fill)
     _capi.check(lib.nmfmu_sp_div_backward(seg.data_ptr(), seg.shape[0], multi.data_ptr() if multi.shape[0] else None,
-                                          multi.shape[0], T.entries(idx), T.entries(vals),
-                                          T.entries(perm) if perm is not None else None,
+                                          multi.shape[0], entries(idx, T.spare), entries(vals, T.spare),
+                                          entries(perm, T.spare) if perm is not None else None,
                                           s.data_ptr() if s is not None else None, panel.data_ptr(), R, beta,
                                           pos.data_ptr(), plane, up.data_ptr(), ws.data_ptr() if ws is not None else None,
                                           out.data_ptr(), r_pad, _stream()), 'nmfmu_sp_div_backward')
@@ -289,8 +293,8 @@ def _masked_call(T: SparseTarget, side: str, owner: Tensor, panel: Tensor, beta:
     ws = _ws if _ws is not None else (torch.empty(n_float, dtype=torch.float32, device=dev) if n_float else None)
     if _fill is not None and ws is not None:
         ws.fill_(_fill)
-    head = (seg.data_ptr(), seg.shape[0], multi.data_ptr() if multi.shape[0] else None, multi.shape[0], T.entries(idx),
-            T.entries(vals), owner.data_ptr(), panel.data_ptr(), R, beta)
+    head = (seg.data_ptr(), seg.shape[0], multi.data_ptr() if multi.shape[0] else None, multi.shape[0], entries(idx, T.spare),
+            entries(vals, T.spare), owner.data_ptr(), panel.data_ptr(), R, beta)
     wsp = ws.data_ptr() if ws is not None else None
     if step is not None:
         l1, l2, gamma = step
@@ -316,9 +320,9 @@ def _masked_loss(Hc: Tensor, Wc: Tensor, T: SparseTarget, beta: float, part=None
         part = torch.empty((n_seg + 3) // 4, dtype=torch.float64, device=Hc.device)
     if out is None:
         out = torch.empty(1, dtype=torch.float64, device=Hc.device)
-    _capi.check(lib.nmfmu_sp_masked_loss(T.seg_h.data_ptr(), n_seg, T.entries(colidx), T.entries(vals), Hc.data_ptr(),
-                                         Wc.data_ptr(), Hc.shape[1], beta, T.masked_v_term(beta), part.data_ptr(),
-                                         out.data_ptr(), _stream()), 'nmfmu_sp_masked_loss')
+    _capi.check(lib.nmfmu_sp_masked_loss(T.seg_h.data_ptr(), n_seg, entries(colidx, T.spare), entries(vals, T.spare),
+                                         Hc.data_ptr(), Wc.data_ptr(), Hc.shape[1], beta, T.masked_v_term(beta),
+                                         part.data_ptr(), out.data_ptr(), _stream()), 'nmfmu_sp_masked_loss')
     return out
 
 

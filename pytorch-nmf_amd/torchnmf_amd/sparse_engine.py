@@ -31,16 +31,6 @@ from . import sparse_autograd as SA
 from .engine import DEFAULT_BACKEND_FACTORY, FactorBuf, StepBuf, _ptr, mu_gamma
 
 
-def _csr(rows: torch.Tensor, cols: torch.Tensor, vals: torch.Tensor, n_rows: int):
-    """(rowptr int32, colidx int32, vals) sorted by (row, col).  One-time set-up on the device."""
-    order = torch.argsort(rows * (int(cols.max()) + 1 if cols.numel() else 1) + cols)
-    rows, cols, vals = rows[order], cols[order], vals[order]
-    counts = torch.bincount(rows, minlength=n_rows)
-    rowptr = torch.zeros(n_rows + 1, dtype=torch.int64, device=rows.device)
-    rowptr[1:] = torch.cumsum(counts, 0)
-    return rowptr.to(torch.int32).contiguous(), cols.to(torch.int32).contiguous(), vals.contiguous()
-
-
 class SparseMU:
     """Same interface as ``DenseMU`` (target_flags / w_step / h_step / divergence) for a sparse target."""
 
@@ -65,10 +55,10 @@ class SparseMU:
         idx, vals = V.indices(), V.values().float()
         self.bad = bool((~(vals >= 0)).any().item()) if vals.numel() else False    # nmf.py:329-330
         self.has_zero = bool(V._nnz() < N * Cc or (vals == 0).any().item())
-        self.csr_h = _csr(idx[0], idx[1], vals, N)       # owner = rows of V  (H half-step, loss)
-        self.csr_w = _csr(idx[1], idx[0], vals, Cc)      # owner = rows of V^T (W half-step)
+        # csr_h: owner = rows of V (H half-step, loss); csr_w: owner = rows of V^T (W half-step).  One-time set-up
+        self.csr_h, self.csr_w, _ = SA.csr_csc(idx[0], idx[1], vals, N, Cc)
         self.vals = vals
-        self._no_entries = torch.zeros(4, dtype=torch.float32, device=dev)
+        self.spare = torch.zeros(4, dtype=torch.float32, device=dev)     # see SA.entries
         # beta in {1, 2}: the images are never read (bf16 keeps them small).  Generic beta: the dense denominator pass
         # reads them -- fp32-grade split-bf16 where the fused kernel has it (padded rank <= 128), else bf16.
         prec = _capi.PREC_BF16
@@ -100,13 +90,7 @@ class SparseMU:
         self.loss_out = torch.zeros(1, dtype=torch.float64, device=dev)
         self.be.pack_factor(self.fW, R, self.r_pad, prec)   # column sums (beta == 1 denominators), operand images
         self.be.pack_factor(self.fH, R, self.r_pad, prec)
-        vd = vals.double()                                  # nmf.py:172-181
-        if self.kl:
-            self.v_norm = float((vd @ vd.log() - vd.sum()).item())
-        elif self.beta == 2.0:
-            self.v_norm = float((vd @ vd).item() * 0.5)
-        else:
-            self.v_norm = float(vd.pow(self.beta).sum().item() / self.beta / (self.beta - 1))
+        self.v_norm = SA.v_norm(vals, self.beta)            # nmf.py:172-181
 
     @staticmethod
     def _s() -> int:
@@ -115,16 +99,12 @@ class SparseMU:
     def target_flags(self):
         return self.bad, self.has_zero
 
-    def _entries(self, t: torch.Tensor) -> int:
-        """Pointer to the column indices / values of a CSR copy.  A target without a stored entry has empty tensors, whose
-        pointer is null; the kernels never read past rowptr's ranges, so any valid address serves them."""
-        return t.data_ptr() if t.numel() else self._no_entries.data_ptr()
-
     def _numerator(self, st: StepBuf, csr):
         """num1 rows < owner.rows (every padded rank column written): the gather kernel over the owner's CSR rows."""
         rowptr, colidx, vals = csr
         own, pan = st.owner, st.panel
-        _capi.check(self.lib.nmfmu_sp_partial(rowptr.data_ptr(), self._entries(colidx), self._entries(vals), own.rows,
+        _capi.check(self.lib.nmfmu_sp_partial(rowptr.data_ptr(), SA.entries(colidx, self.spare),
+                                              SA.entries(vals, self.spare), own.rows,
                                               own.f.data_ptr(), pan.f.data_ptr(), self.rank, self.beta,
                                               st.num1.data_ptr(), self.r_pad, self._s()), 'nmfmu_sp_partial')
 
@@ -163,7 +143,8 @@ class SparseMU:
         """loss_out = the sum over the stored entries (nmf.py:619, 626, 636): the O(nnz) term in HIP, one double partial per
         four rows in loss_part.  Enqueued only."""
         rowptr, colidx, vals = self.csr_h
-        _capi.check(self.lib.nmfmu_sp_loss_neg(rowptr.data_ptr(), self._entries(colidx), self._entries(vals), self.fH.rows,
+        _capi.check(self.lib.nmfmu_sp_loss_neg(rowptr.data_ptr(), SA.entries(colidx, self.spare),
+                                               SA.entries(vals, self.spare), self.fH.rows,
                                                self.fH.f.data_ptr(), self.fW.f.data_ptr(), self.rank, self.beta,
                                                self.loss_part.data_ptr(), self.loss_out.data_ptr(), self._s()),
                     'nmfmu_sp_loss_neg')

@@ -61,7 +61,7 @@ def coalesce(idx, vals, shape):
 
 
 def csr(rows, cols, vals, n_rows: int):
-    """(rowptr int32, colidx int32, vals fp32) sorted by (row, col): the mirror of sparse_engine._csr."""
+    """(rowptr int32, colidx int32, vals fp32) sorted by (row, col): the mirror of either half of sparse_autograd.csr_csc."""
     rows = np.asarray(rows, dtype=np.int64)
     cols = np.asarray(cols, dtype=np.int64)
     vals = np.asarray(vals, dtype=np.float32)

@@ -167,6 +167,33 @@ def test_determinism_subsets_and_nan_prefill(dev, beta, R):
     assert torch.equal(gH, gHn) and torch.equal(gW, gWn)
 
 
+def test_nonfinite_panel_row0_reaches_only_rows_that_store_column0(dev):
+    """The kernels hand the panel rows of four entries to the wave per trip; an entry past the end of a row's last group
+    takes no panel row at all (nmfmu_sparse_common.h: fetch_group), so it is not row 0 times g = 0.  With W[0, 2] = +inf
+    (the same finite pos and s) every row of grad_H that does not store column 0 keeps its bits; 0 * inf = NaN would
+    reach each of them whose entry count is not a multiple of four (one segment per row at chunk 512)."""
+    from torchnmf_amd import sparse_autograd as SA
+    R, beta = 33, 1.0
+    idx, _, (N, _) = _pattern('small')
+    H0, W0 = _factors('small', R)
+    T = _target('small', dev)
+    Hc, Wc = H0.to(dev), W0.to(dev)
+    _, s, (_, small_w) = SA._forward(Hc, Wc, T, beta, want_s=True)
+    up = torch.tensor([UP], device=dev)
+    Winf = Wc.clone()
+    Winf[0, 2] = float('inf')
+    g_fin = SA._backward_side(Hc, Wc, small_w, T, 'h', beta, s, up)
+    g_inf = SA._backward_side(Hc, Winf, small_w, T, 'h', beta, s, up)
+    with0 = np.unique(idx[0][idx[1] == 0])
+    without0 = np.setdiff1d(np.arange(N), with0)
+    counts = np.bincount(idx[0], minlength=N)
+    assert len(with0) and np.any(counts[without0] % 4 != 0) and T.multi_h.shape[0] == 0
+    assert not torch.isfinite(g_inf[torch.from_numpy(with0).to(dev), 2]).any()       # the value did go in
+    rows = torch.from_numpy(without0).to(dev)
+    same = (g_fin[rows].view(torch.int32) == g_inf[rows].view(torch.int32)).all(dim=1)
+    assert bool(same.all()), ('rows that differ', without0[(~same).cpu().numpy()].tolist())
+
+
 @pytest.mark.parametrize('beta', [1, 2])
 def test_chunk4_against_chunk512(dev, beta):
     """chunk = 4 sends every row with more than four entries through the workspace and the finishing kernel; both chunkings

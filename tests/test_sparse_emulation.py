@@ -109,11 +109,11 @@ def test_csr_mirror_properties():
     dense_t = np.zeros((C, N), np.float32)
     dense_t[S.row_of_entry(rpt), cit] = cvt
     assert np.array_equal(dense_t, dense.T)       # the CSR of V^T is the transpose of the CSR of V
-    # the engine's own host code on the CPU gives the same three arrays, entry order of the input notwithstanding
-    from torchnmf_amd.sparse_engine import _csr
-    perm = np.random.default_rng(0).permutation(len(cvals))
-    for (r, c, n), want in (((0, 1, N), (rp, ci, cv)), ((1, 0, C), (rpt, cit, cvt))):
-        got = _csr(torch.from_numpy(cidx[r][perm]), torch.from_numpy(cidx[c][perm]), torch.from_numpy(cvals[perm]), n)
+    # the engine's own host code on the CPU gives the same three arrays for both orientations (its input is the coalesced
+    # order, which is what SparseMU and SparseTarget hand it)
+    from torchnmf_amd.sparse_autograd import csr_csc
+    got_csr, got_csc, _ = csr_csc(torch.from_numpy(cidx[0]), torch.from_numpy(cidx[1]), torch.from_numpy(cvals), N, C)
+    for got, want in ((got_csr, (rp, ci, cv)), (got_csc, (rpt, cit, cvt))):
         for g_, w_ in zip(got, want):
             assert g_.numpy().dtype == w_.dtype and np.array_equal(g_.numpy(), w_)
     e = S.csr(np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.float32), 5)
