@@ -61,6 +61,8 @@ extern "C" {
                                   the two products above, finished with the latent vector Z);
                                   nmfmu_sp_masked_terms / nmfmu_sp_masked_step / nmfmu_sp_masked_loss / nmfmu_sp_masked_ws
                                   (missing-data NMF: sparse targets fitted over their stored entries only, every beta);
+                                  nmfmu_sp_plca_estep / nmfmu_sp_plca_gather (PLCA.fit on sparse-COO targets: the E-step over
+                                  the stored entries; added at ABI 10, additive);
                                10: nmfmu_plca_normalize / nmfmu_plca_z / nmfmu_plca3 take alpha as double (an argument changed its
                                   type: not additive).  The Dirichlet prior adds fp32(alpha - 1) with the subtraction in double,
                                   as the reference's in-place add does; fp32(alpha) - 1.f was off by 4.7e-5 relative at
@@ -799,6 +801,30 @@ int nmfmu_plca_scale(float* f, int rows, int rank, const float* colsum, void* st
 /* plca.py:253-260 in one launch: prior[r] = z[r] * relu(zgrad[r]); z <- prior (+ alpha - 1, clamped below at eps when
  * alpha != 1), then z /= sum(z).  rank <= 256. */
 int nmfmu_plca_z(float* z, const float* zgrad, int rank, double alpha, float* prior, void* stream);
+
+/* ---- PLCA on a sparse-COO target: the E-step over the STORED entries only (additive entries) ----------------------------------
+ * Where Vn is zero, G = Vn / (H diag(Z) W^T + eps) is zero and adds nothing to G W, G^T H or Z.grad: both unscaled numerators of
+ * an EM iteration are sums over the stored set, exactly.  seg / multi are the segment lists of nmfmu_sp_div_backward; vals_n are
+ * the stored values divided by their total, in CSR order; the factors are the fp32 masters [rows][rank].  One reconstruction
+ * feeds every update of the iteration (plca.py:252): g is formed once, on the H side, and the W side reads it back.
+ *   nmfmu_sp_plca_estep  : H side, the CSR list.  Per stored entry p of row i, j = colidx[p]:
+ *                          s_p = sum_r (owner[i][r] * z[r]) * panel[j][r] (the row scaled once per segment; fixed-order butterfly),
+ *                          g_p = vals_n[p] / (s_p + eps), g_out[p] = g_p (one float per stored entry, CSR order, written once),
+ *                          num[i][:] = sum_p g_p * panel[j][:]  = (G W)[i].  owner = H, panel = W, z [rank].
+ *   nmfmu_sp_plca_gather : W side, the CSC list.  num[j][:] = sum_p g[perm[p]] * panel[rowidx[p]][:] = (G^T H)[j]; perm[p] = the
+ *                          CSR position of CSC entry p; panel = H.  No dot product, no cross-lane reduction, no divide.
+ * num is [owner rows][r_pad]: every padded column is written (0), a row without entries gets zeros -- the single slab
+ * nmfmu_plca_em reads (nslab = 1, rows_pad = rows).  Entries accumulate in storage order, a split row's partial rows
+ * (ws[slot][r_pad]; the size rule is nmfmu_sp_div_backward_ws) in segment order: plain stores only, no atomics -- a repeated
+ * call is bitwise identical.
+ * Null pointers, n_seg <= 0, rank <= 0, r_pad != nmfmu_pad_rank(rank): NMFMU_ERR_ARG; rank > 256: NMFMU_ERR_UNSUPPORTED -- both
+ * before any device work. */
+int nmfmu_sp_plca_estep(const int32_t* seg, int n_seg, const int32_t* multi, int n_multi, const int32_t* colidx,
+                        const float* vals_n, const float* owner, const float* z, const float* panel, int rank, float* g_out,
+                        float* ws, float* num, int r_pad, void* stream);
+int nmfmu_sp_plca_gather(const int32_t* seg, int n_seg, const int32_t* multi, int n_multi, const int32_t* rowidx,
+                         const int32_t* perm, const float* g, const float* panel, int rank, float* ws, float* num, int r_pad,
+                         void* stream);
 
 /* ---- shift-invariant PLCA (SIPLCA / SIPLCA2 / SIPLCA3, plca.py:376-606) on the NMFD GEMM path ----------------------
  * Same EM update as PLCA with W (C, R, *T), H (B, R, *Lh): factors are addressed [outer][rank][inner], the unscaled

@@ -1,4 +1,5 @@
-// The protocol the sparse kernels share (nmfmu_sparse.hip, nmfmu_sparse_autograd.hip, nmfmu_sparse_masked.hip), once:
+// The protocol the sparse kernels share (nmfmu_sparse.hip, nmfmu_sparse_autograd.hip, nmfmu_sparse_masked.hip,
+// nmfmu_sparse_plca.hip), once:
 //
 //   a wave per owner row or SEGMENT of one, the lanes across the rank, RL rank slots per lane (slot q of a lane is rank
 //   column lane + 64 q; r_pad 32 uses half a wave's lanes with zeros beyond the rank); the stored entries of a segment are

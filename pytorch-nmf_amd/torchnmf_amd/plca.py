@@ -7,6 +7,8 @@ GEMM only.  Both contractions run on ``nmfmu::fused_kernel`` (through ``nmfmu_mu
 the Z-scaled factor for the reconstruction, image of the unscaled factor for the second GEMM); the O((N + C) R)
 remainder of plca.py:248-290 (multiply by relu(grad), divide by the latent prior, Dirichlet prior, renormalise) runs in
 the small ``nmfmu_plca_*`` kernels, and only the R-element latent vector is updated with torch scalar ops.
+On a sparse-COO target the iteration is exactly sparse -- G is zero wherever the target is -- and ``_SparsePlcaEM`` forms both
+numerators from the stored entries (``nmfmu_sp_plca_estep`` / ``nmfmu_sp_plca_gather``) in front of the same small kernels.
 ``SIPLCA`` / ``SIPLCA2`` / ``SIPLCA3`` (plca.py:376-606) are to PLCA what NMFD / NMF2D / NMF3D are to NMF: the same EM
 update on the NMFD GEMM engine (``_ConvPlcaEM``), with W * Z as the reconstruction operand.
 """
@@ -126,7 +128,11 @@ class BaseComponent(nn.Module):
     def fit(self, V, tol=1e-4, max_iter=200, verbose=False, W_alpha=1., H_alpha=1., Z_alpha=1., *, precision=None):
         """EM fit (plca.py:193-304).  Returns ``(n_iter, norm)`` like the reference: the index of the last iteration and
         ``V.sum()``.  ``W_alpha`` / ``H_alpha`` / ``Z_alpha``: floats or one-element tensors (what the reference's
-        ``if alpha != 1`` admits); a tensor with more elements raises the same RuntimeError as there."""
+        ``if alpha != 1`` admits); a tensor with more elements raises the same RuntimeError as there.
+
+        ``PLCA.fit`` also takes a 2-D sparse-COO tensor or a ``metrics.SparseTarget`` (rank <= 256): the same EM iterations
+        computed from the stored entries alone, in exact fp32 (``precision`` is not consulted), without the dense target ever
+        existing; ``norm`` is then the sum of the stored values.  The shift-invariant models refuse sparse targets."""
         W, H, Z = self.W, self.H, self.Z
         assert W is not None and H is not None and Z is not None
         # Dirichlet hyper-parameters (plca.py:197-199 types them Union[float, Tensor]).  The reference tests them with
@@ -138,6 +144,9 @@ class BaseComponent(nn.Module):
         # hyper-parameter of a FROZEN factor is never looked at there, so it is neither validated nor converted here
         W_alpha, H_alpha, Z_alpha = (_scalar_alpha(a, n, f) if f.requires_grad else 1.0
                                      for a, n, f in ((W_alpha, 'W_alpha', W), (H_alpha, 'H_alpha', H), (Z_alpha, 'Z_alpha', Z)))
+        if _is_sparse_target(V):
+            em, norm = self._make_sparse_em(V)            # exact fp32 over the stored entries: ``precision`` is not consulted
+            return self._run_em(em, norm, tol, max_iter, verbose, W_alpha, H_alpha, Z_alpha)
         for t_, what in ((V, 'fit'), (W, 'fit'), (H, 'fit'), (Z, 'fit')):
             _require_device(t_, what)
         V = V.detach().float()
@@ -148,6 +157,14 @@ class BaseComponent(nn.Module):
             if not p.data.is_contiguous():
                 p.data = p.data.contiguous()
         em = self._make_em(Vn, precision)
+        return self._run_em(em, norm, tol, max_iter, verbose, W_alpha, H_alpha, Z_alpha)
+
+    def _make_sparse_em(self, V):
+        raise NotImplementedError('sparse targets are supported by PLCA only')
+
+    def _run_em(self, em, norm, tol, max_iter, verbose, W_alpha, H_alpha, Z_alpha):
+        """The EM loop of plca.py:245-304 on an EM state (dense or sparse): the stop rule and the ``verbose`` bar."""
+        W, H, Z = self.W, self.H, self.Z
         nrm = float(norm.item())
         loss_init = previous = _sqrt2(nrm * em.divergence())      # kl_div(WZH * norm, V), plca.py:245-246
         pbar = None
@@ -172,7 +189,60 @@ class BaseComponent(nn.Module):
         return n_iter, norm
 
 
-class _PlcaEM:
+def _is_sparse_target(V) -> bool:
+    from .sparse_autograd import SparseTarget
+    return isinstance(V, SparseTarget) or (isinstance(V, Tensor) and V.is_sparse)
+
+
+class _PlcaMStep:
+    """The M-step of an EM iteration (plca.py:253-290) from the two unscaled numerators, shared by the dense and the sparse EM
+    state: the ``nmfmu_plca_em`` / ``_z`` / ``_normalize`` / ``_scale`` launches in the reference's order.  The state
+    provides ``lib``, ``R``, ``r_pad``, the fp32 masters ``W`` / ``H`` / ``Z`` and the scratch ``part``, ``cs``, ``cs2``,
+    ``zg``, ``prior``."""
+
+    def _s(self):
+        return torch.cuda.current_stream().cuda_stream
+
+    def _em_num(self, f, num, nslab, rows_pad, z_old, update, want_zgrad):
+        """f *= relu(num * z_old) (when ``update``); column sums of the result -> self.cs; Z.grad partials -> self.zg.
+        ``num``: ``nslab`` planes ``[rows_pad, r_pad]`` of the unscaled numerator."""
+        _capi.check(self.lib.nmfmu_plca_em(f.data_ptr(), f.shape[0], self.R, self.r_pad, num.data_ptr(), nslab, rows_pad,
+                                           z_old.data_ptr(), int(update), self.part.data_ptr(), self.cs.data_ptr(),
+                                           self.zg.data_ptr() if want_zgrad else None, self._s()), 'nmfmu_plca_em')
+
+    def _normalize(self, f, alpha):
+        """plca.py:265-275 / 279-289 after the multiplication: divide by the latent prior held in ``self.prior``."""
+        _capi.check(self.lib.nmfmu_plca_normalize(f.data_ptr(), f.shape[0], self.R, self.r_pad, self.prior.data_ptr(),
+                                                  float(alpha), self.part.data_ptr(), self.cs2.data_ptr(), self._s()),
+                    'nmfmu_plca_normalize')
+        if alpha != 1:
+            _capi.check(self.lib.nmfmu_plca_scale(f.data_ptr(), f.shape[0], self.R, self.cs2.data_ptr(), self._s()),
+                        'nmfmu_plca_scale')
+
+    def _m_step(self, num_w, num_h, z_old, tW, tH, tZ, W_alpha, H_alpha, Z_alpha):
+        """``num_w`` / ``num_h``: (planes, nslab, rows_pad) of G^T H and G W; ``z_old``: the Z the numerators were formed
+        with (a buffer of its own: Z is updated in place here)."""
+        # W's multiplication pass also yields Z.grad = sum W_old * (G^T H); the division by the latent prior, which needs
+        # the new Z first (plca.py:253-270), is the separate normalize kernel
+        self._em_num(self.W.data, *num_w, z_old, tW, True)
+        have_prior = False
+        if tZ:                                          # plca.py:253-260: one launch; prior = Z_old * relu(Z.grad)
+            _capi.check(self.lib.nmfmu_plca_z(self.Z.data.data_ptr(), self.zg.data_ptr(), self.R, float(Z_alpha),
+                                              self.prior.data_ptr(), self._s()), 'nmfmu_plca_z')
+            have_prior = True
+        if tW:
+            if not have_prior:                          # frozen Z: get_norm of the multiplied W (plca.py:266-268)
+                self.prior[:self.R].copy_(self.cs[:self.R])
+                have_prior = True
+            self._normalize(self.W.data, W_alpha)
+        if tH:
+            self._em_num(self.H.data, *num_h, z_old, True, False)
+            if not have_prior:                          # frozen Z and W: get_norm of the multiplied H
+                self.prior[:self.R].copy_(self.cs[:self.R])
+            self._normalize(self.H.data, H_alpha)
+
+
+class _PlcaEM(_PlcaMStep):
     """Device state of one PLCA fit: packed Vn (both orientations), factor images (scaled and unscaled), slabs."""
 
     def __init__(self, Vn, W, H, Z, precision):
@@ -234,9 +304,6 @@ class _PlcaEM:
         self.ones = torch.ones(self.r_pad, dtype=torch.float32, device=dev)
         self.repack()
 
-    def _s(self):
-        return torch.cuda.current_stream().cuda_stream
-
     def repack(self):
         self.zpad[:self.R] = self.Z
         # (both image sets through the scaled entry -- scale = ones for the plain one: it skips the column-sum finalize
@@ -250,46 +317,94 @@ class _PlcaEM:
         self.be.loss(self.step_l, self.loss_part, self.loss_out)
         return float(self.loss_out.item())
 
-    def _em(self, f, st, z_old, update, want_zgrad):
-        """f *= relu(num * z_old) (when ``update``); column sums of the result -> self.cs; Z.grad partials -> self.zg."""
-        _capi.check(self.lib.nmfmu_plca_em(f.data_ptr(), f.shape[0], self.R, self.r_pad, st.slab_num.data_ptr(), st.nsplit,
-                                           st.owner.rows_pad, z_old.data_ptr(), int(update), self.part.data_ptr(),
-                                           self.cs.data_ptr(), self.zg.data_ptr() if want_zgrad else None, self._s()),
-                    'nmfmu_plca_em')
-
-    def _normalize(self, f, alpha):
-        """plca.py:265-275 / 279-289 after the multiplication: divide by the latent prior held in ``self.prior``."""
-        _capi.check(self.lib.nmfmu_plca_normalize(f.data_ptr(), f.shape[0], self.R, self.r_pad, self.prior.data_ptr(),
-                                                  float(alpha), self.part.data_ptr(), self.cs2.data_ptr(), self._s()),
-                    'nmfmu_plca_normalize')
-        if alpha != 1:
-            _capi.check(self.lib.nmfmu_plca_scale(f.data_ptr(), f.shape[0], self.R, self.cs2.data_ptr(), self._s()),
-                        'nmfmu_plca_scale')
-
     def em_step(self, tW, tH, tZ, W_alpha, H_alpha, Z_alpha):
         """One EM iteration (plca.py:248-290): every update uses the gradients of ONE reconstruction."""
         self.be.mu_partial(self.step_w)
         self.be.mu_partial(self.step_h)
-        z_old = self.zpad                               # (still the old Z: repack() below refreshes it)
-        # W's multiplication pass also yields Z.grad = sum W_old * (G^T H); the division by the latent prior, which needs
-        # the new Z first (plca.py:253-270), is the separate normalize kernel
-        self._em(self.W.data, self.step_w, z_old, tW, True)
-        have_prior = False
-        if tZ:                                          # plca.py:253-260: one launch; prior = Z_old * relu(Z.grad)
-            _capi.check(self.lib.nmfmu_plca_z(self.Z.data.data_ptr(), self.zg.data_ptr(), self.R, float(Z_alpha),
-                                              self.prior.data_ptr(), self._s()), 'nmfmu_plca_z')
-            have_prior = True
-        if tW:
-            if not have_prior:                          # frozen Z: get_norm of the multiplied W (plca.py:266-268)
-                self.prior[:self.R].copy_(self.cs[:self.R])
-                have_prior = True
-            self._normalize(self.W.data, W_alpha)
-        if tH:
-            self._em(self.H.data, self.step_h, z_old, True, False)
-            if not have_prior:                          # frozen Z and W: get_norm of the multiplied H
-                self.prior[:self.R].copy_(self.cs[:self.R])
-            self._normalize(self.H.data, H_alpha)
+        slabs = lambda st: (st.slab_num, st.nsplit, st.owner.rows_pad)
+        # (zpad is still the old Z: repack() below refreshes it)
+        self._m_step(slabs(self.step_w), slabs(self.step_h), self.zpad, tW, tH, tZ, W_alpha, H_alpha, Z_alpha)
         self.repack()
+
+
+class _SparsePlcaEM(_PlcaMStep):
+    """Device state of one PLCA fit on a sparse-COO target.  Where Vn is zero, G = Vn / (H diag(Z) W^T + eps) is zero, so the
+    numerators of an EM iteration are sums over the stored entries -- exactly -- at O(nnz R + (N + C) R):
+    ``nmfmu_sp_plca_estep`` forms g once per stored entry and G W, ``nmfmu_sp_plca_gather`` reads g back for G^T H, and the
+    M-step is the dense one on single-slab numerators.  Works on the fp32 masters directly: no images, nothing to repack.
+
+    ``T``: the ``SparseTarget``; ``vals_n``: its stored values over their total, fp32, CSR order."""
+
+    def __init__(self, T, vals_n, W, H, Z):
+        from . import sparse_autograd as SA
+        self.SA = SA
+        self.lib = lib = _capi.load()
+        N, Cc = T.shape
+        R = W.shape[1]
+        assert W.shape == (Cc, R) and H.shape == (N, R) and Z.shape == (R,) and vals_n.shape == (T.nnz,)
+        self.T, self.vals_n = T, vals_n.contiguous()
+        self.W, self.H, self.Z = W, H, Z
+        self.R, self.r_pad = R, lib.nmfmu_pad_rank(R)
+        _capi.check(min(self.r_pad, 0), 'nmfmu_pad_rank')
+        dev = W.device
+        f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        self.g = f32(max(T.nnz, 1))                       # g_p = vn_p / (s_p + eps), CSR order
+        self.num_h, self.num_w = f32(N, self.r_pad), f32(Cc, self.r_pad)
+        self.ws_h = f32(max(SA.workspace_floats(T.n_ws_h, self.r_pad), 1))
+        self.ws_w = f32(max(SA.workspace_floats(T.n_ws_w, self.r_pad), 1))
+        self.part = f32(max(lib.nmfmu_plca_part_bytes(max(N, Cc), self.r_pad) // 4, 4))
+        self.cs, self.cs2, self.zg = (torch.zeros(self.r_pad, dtype=torch.float32, device=dev) for _ in range(3))
+        self.prior = torch.ones(self.r_pad, dtype=torch.float32, device=dev)
+        self.z_old = torch.zeros(self.r_pad, dtype=torch.float32, device=dev)
+        # the loss: sum_stored vn log(s + eps) on the device, the terms of vn alone once on the host (float64), sum_all s
+        # from the column sums
+        self.v_term = SA.masked_v_term(self.vals_n, 1.0)
+        self.loss_part = torch.empty((T.seg_h.shape[0] + 3) // 4, dtype=torch.float64, device=dev)
+        self.loss_neg = torch.empty(1, dtype=torch.float64, device=dev)
+        self.sum_part = f32(R * 128)
+        self.cs_h, self.cs_w = f32(R), f32(R)
+
+    def _lists(self, side):
+        (ptr, idx, vals), seg, multi, n_ws = self.T.side(side)
+        return seg, multi.data_ptr() if multi.shape[0] else None, multi.shape[0], self.SA.entries(idx, self.T.spare)
+
+    def numerators(self):
+        """One reconstruction: g and G W (H side), then G^T H (W side) from the same g.  Enqueued only."""
+        T, SA = self.T, self.SA
+        seg, multi, n_multi, colidx = self._lists('h')
+        _capi.check(self.lib.nmfmu_sp_plca_estep(seg.data_ptr(), seg.shape[0], multi, n_multi, colidx,
+                                                 SA.entries(self.vals_n, T.spare), self.H.data_ptr(), self.z_old.data_ptr(),
+                                                 self.W.data_ptr(), self.R, self.g.data_ptr(), self.ws_h.data_ptr(),
+                                                 self.num_h.data_ptr(), self.r_pad, self._s()), 'nmfmu_sp_plca_estep')
+        seg, multi, n_multi, rowidx = self._lists('w')
+        _capi.check(self.lib.nmfmu_sp_plca_gather(seg.data_ptr(), seg.shape[0], multi, n_multi, rowidx,
+                                                  SA.entries(T.perm, T.spare), self.g.data_ptr(), self.H.data_ptr(), self.R,
+                                                  self.ws_w.data_ptr(), self.num_w.data_ptr(), self.r_pad, self._s()),
+                    'nmfmu_sp_plca_gather')
+
+    def divergence(self) -> float:
+        """kl_div(H diag(Z) W^T, Vn) over ALL N x C entries, as ``_PlcaEM.divergence()`` gives it on the densified target:
+        sum x (log(x + eps) - log(s + eps)) - x + s, where the unstored entries leave s alone and
+        sum_all s = sum_r Z_r colsum(H)_r colsum(W)_r."""
+        T, SA, lib = self.T, self.SA, self.lib
+        rowptr, colidx, _ = T.csr
+        Hz = (self.H * self.Z).contiguous()
+        _capi.check(lib.nmfmu_sp_div_forward(T.seg_h.data_ptr(), T.seg_h.shape[0], SA.entries(colidx, T.spare),
+                                             SA.entries(self.vals_n, T.spare), Hz.data_ptr(), self.W.data_ptr(), self.R, 1.0,
+                                             None, self.loss_part.data_ptr(), self.loss_neg.data_ptr(), self._s()),
+                    'nmfmu_sp_div_forward')
+        for f, cs in ((self.H, self.cs_h), (self.W, self.cs_w)):
+            _capi.check(lib.nmfmu_rank_sums(f.data_ptr(), f.shape[0], self.R, 1, self.sum_part.data_ptr(), cs.data_ptr(),
+                                            self._s()), 'nmfmu_rank_sums')
+        pos = (self.cs_h.double() * self.cs_w.double()) @ self.Z.double()
+        return float((self.v_term + pos - self.loss_neg[0]).item())
+
+    def em_step(self, tW, tH, tZ, W_alpha, H_alpha, Z_alpha):
+        """One EM iteration (plca.py:248-290): every update uses the gradients of ONE reconstruction."""
+        self.z_old[:self.R].copy_(self.Z)               # the M-step updates Z in place
+        self.numerators()
+        self._m_step((self.num_w, 1, self.num_w.shape[0]), (self.num_h, 1, self.num_h.shape[0]), self.z_old, tW, tH, tZ,
+                     W_alpha, H_alpha, Z_alpha)
 
 
 def plain_struct(fb: FactorBuf):
@@ -378,6 +493,35 @@ class PLCA(BaseComponent):
     def _make_em(self, Vn, precision):
         assert Vn.dim() == 2 and Vn.shape == (self.H.shape[0], self.W.shape[0])
         return _PlcaEM(Vn, self.W.data, self.H.data, self.Z.data, precision)
+
+    def _make_sparse_em(self, V):
+        """(EM state, norm) for a 2-D sparse-COO tensor or a ``metrics.SparseTarget``: the stored values over their total,
+        fp32, in CSR order.  Checks in the order device, sign, total, rank -- all before anything is prepared."""
+        from .sparse_autograd import MAX_RANK, SparseTarget
+        W, H, Z = self.W, self.H, self.Z
+        for t_ in (V, W, H, Z):
+            _require_device(t_, 'fit')
+        if isinstance(V, SparseTarget):
+            T, vals = V, V.vals
+        else:
+            assert V.dim() == 2, 'a sparse target must be a 2-D sparse COO tensor'
+            T, V = None, V.detach().coalesce()
+            vals = V.values().float()
+        assert bool(torch.all(vals >= 0.)), "Target should be non-negative."
+        norm = vals.sum()
+        if not float(norm.item()) > 0:
+            raise ValueError('the stored values of the target sum to 0: there is nothing to normalise')
+        if self.rank > MAX_RANK:
+            raise NotImplementedError(f'PLCA.fit on a sparse target: rank {self.rank} > {MAX_RANK}, the limit of the sparse '
+                                      f'kernels')
+        assert tuple(V.shape) == (H.shape[0], W.shape[0]), \
+            f'target {tuple(V.shape)} does not match H {tuple(H.shape)} and W {tuple(W.shape)}'
+        if T is None:
+            T = SparseTarget(V)
+        for p in (W, H, Z):
+            if not p.data.is_contiguous():
+                p.data = p.data.contiguous()
+        return _SparsePlcaEM(T, T.vals / norm, W.data, H.data, Z.data), norm
 
 
 class _ConvPlcaEM:
