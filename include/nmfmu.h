@@ -63,6 +63,8 @@ extern "C" {
                                   (missing-data NMF: sparse targets fitted over their stored entries only, every beta);
                                   nmfmu_sp_plca_estep / nmfmu_sp_plca_gather (PLCA.fit on sparse-COO targets: the E-step over
                                   the stored entries; added at ABI 10, additive);
+                                  nmfmu_score_pairs / nmfmu_topk / nmfmu_topk_ws (scoring a fitted model: values at (row, column)
+                                  pairs and the k best columns per row; added at ABI 10, additive);
                                10: nmfmu_plca_normalize / nmfmu_plca_z / nmfmu_plca3 take alpha as double (an argument changed its
                                   type: not additive).  The Dirichlet prior adds fp32(alpha - 1) with the subtraction in double,
                                   as the reference's in-place add does; fp32(alpha) - 1.f was off by 4.7e-5 relative at
@@ -825,6 +827,28 @@ int nmfmu_sp_plca_estep(const int32_t* seg, int n_seg, const int32_t* multi, int
 int nmfmu_sp_plca_gather(const int32_t* seg, int n_seg, const int32_t* multi, int n_multi, const int32_t* rowidx,
                          const int32_t* perm, const float* g, const float* panel, int rank, float* ws, float* num, int r_pad,
                          void* stream);
+
+/* ---- scoring a fitted model without the N x C product (additive entries; scoring.py) ---------------------
+ * H [N][rank] and W [C][rank] are fp32 masters; a score is s_ij = <H[i], W[j]>.
+ *   nmfmu_score_pairs : out[p] = s at (rows[p], cols[p]), p < n; the pairs may repeat and come in any order.  The caller
+ *                       answers for 0 <= rows[p] < N and 0 <= cols[p] < C.  n == 0 launches nothing.
+ *   nmfmu_topk        : for each of the n_rows requested rows (row_ids, or rows 0 .. n_rows - 1 when it is NULL) the k largest
+ *                       scores over the admissible columns, score descending and equal scores by ascending column; a row with
+ *                       fewer than k admissible columns ends in (-inf, -1).  out_val / out_idx are [n_rows][k].  The stored
+ *                       columns of row i of a CSR pattern -- ex_colidx[ex_rowptr[i] .. ex_rowptr[i + 1]), ascending -- are
+ *                       inadmissible.  The columns are cut into nsplit ranges of whole 128-column tiles; with nsplit > 1 the
+ *                       ranges' lists go to ws and a second kernel merges them.  Exact-fp32 MFMA; the result does not depend
+ *                       on nsplit.
+ *   nmfmu_topk_ws     : bytes of ws (0 for nsplit == 1): n_rows * nsplit * k * 8 -- a pure function of its arguments.
+ * Null pointers (row_ids, ex_rowptr and, for nsplit == 1, ws may be NULL), sizes < 1, rank <= 0, k < 1, nsplit < 1:
+ * NMFMU_ERR_ARG; rank > 256 or k > 128: NMFMU_ERR_UNSUPPORTED -- both before any device work.  No atomics: a repeated call is
+ * bitwise identical. */
+int nmfmu_score_pairs(const int32_t* rows, const int32_t* cols, int64_t n, const float* H, int N, const float* W, int C,
+                      int rank, float* out, void* stream);
+int64_t nmfmu_topk_ws(int n_rows, int k, int nsplit);
+int nmfmu_topk(const float* H, int N, const int32_t* row_ids, int n_rows, const float* W, int C, int rank, int k,
+               const int32_t* ex_rowptr, const int32_t* ex_colidx, int nsplit, void* ws, float* out_val, int32_t* out_idx,
+               void* stream);
 
 /* ---- shift-invariant PLCA (SIPLCA / SIPLCA2 / SIPLCA3, plca.py:376-606) on the NMFD GEMM path ----------------------
  * Same EM update as PLCA with W (C, R, *T), H (B, R, *Lh): factors are addressed [outer][rank][inner], the unscaled

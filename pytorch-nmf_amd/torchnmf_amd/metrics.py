@@ -16,6 +16,9 @@ factors, with HIP backward kernels (``nmfmu_sp_div_backward``).  With
 ``unstored='missing'`` the unstored entries are unknown instead of zero: the
 reference's ``beta_div`` over the stored entries alone, for any beta
 (``nmfmu_sp_masked_loss`` / ``nmfmu_sp_masked_terms``).
+
+``score_pairs`` / ``topk_scores`` (``scoring.py``) use a fitted model without the ``N x C`` product: its value at
+(row, column) pairs, and the ``k`` best admissible columns per row.
 """
 from __future__ import annotations
 
@@ -24,8 +27,10 @@ from torch import Tensor
 
 from . import _capi
 from .sparse_autograd import SparseTarget, sparse_beta_div
+from .scoring import score_pairs, topk_scores
 
-__all__ = ['kl_div', 'euclidean', 'is_div', 'beta_div', 'sparseness', 'SparseTarget', 'sparse_beta_div']
+__all__ = ['kl_div', 'euclidean', 'is_div', 'beta_div', 'sparseness', 'SparseTarget', 'sparse_beta_div', 'score_pairs',
+           'topk_scores']
 
 
 def _beta_div_value(input: Tensor, target: Tensor, beta: float) -> Tensor:

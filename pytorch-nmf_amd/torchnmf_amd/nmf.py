@@ -592,6 +592,18 @@ class NMF(BaseComponent):
             return _ReconstructFn.apply(H, W)
         return _reconstruct_forward(H, W)
 
+    def predict(self, rows: Tensor, cols: Tensor) -> Tensor:
+        """The model's value at (row, column) pairs, fp32 ``[n]``, without the ``N x C`` reconstruction
+        (``scoring.score_pairs`` on ``H``, ``W``; detached)."""
+        from .scoring import score_pairs
+        return score_pairs(self.H, self.W, rows, cols)
+
+    def topk(self, k: int, rows: Tensor = None, exclude=None):
+        """``(values, indices)`` of the ``k`` best columns of every requested row, the stored positions of ``exclude``
+        (typically the sparse training target) left out (``scoring.topk_scores`` on ``H``, ``W``; detached)."""
+        from .scoring import topk_scores
+        return topk_scores(self.H, self.W, k, rows=rows, exclude=exclude)
+
     def _make_engine(self, V, beta, l1, l2, precision, group, allreduce=None):
         from .engine import DenseMU
         assert V.dim() == 2 and V.shape == (self.H.shape[0], self.W.shape[0]), \

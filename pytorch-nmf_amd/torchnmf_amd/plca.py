@@ -490,6 +490,19 @@ class PLCA(BaseComponent):
             return _PlcaReconstructFn.apply(H, W, Z)
         return _plca_forward(H, W, Z)
 
+    def predict(self, rows: Tensor, cols: Tensor, norm: Optional[float] = None) -> Tensor:
+        """The model's value at (row, column) pairs, fp32 ``[n]``, without the ``N x C`` reconstruction
+        (``scoring.score_pairs`` on ``H * Z``, ``W``; detached); times ``norm`` when given, as ``forward``."""
+        from .scoring import score_pairs
+        out = score_pairs(self.H.detach() * self.Z.detach(), self.W, rows, cols)
+        return out if norm is None else out * norm
+
+    def topk(self, k: int, rows: Tensor = None, exclude=None):
+        """``(values, indices)`` of the ``k`` best columns of every requested row, the stored positions of ``exclude``
+        left out (``scoring.topk_scores`` on ``H * Z``, ``W``; detached)."""
+        from .scoring import topk_scores
+        return topk_scores(self.H.detach() * self.Z.detach(), self.W, k, rows=rows, exclude=exclude)
+
     def _make_em(self, Vn, precision):
         assert Vn.dim() == 2 and Vn.shape == (self.H.shape[0], self.W.shape[0])
         return _PlcaEM(Vn, self.W.data, self.H.data, self.Z.data, precision)
