@@ -65,6 +65,8 @@ extern "C" {
                                   the stored entries; added at ABI 10, additive);
                                   nmfmu_score_pairs / nmfmu_topk / nmfmu_topk_ws (scoring a fitted model: values at (row, column)
                                   pairs and the k best columns per row; added at ABI 10, additive);
+                                  nmfmu_fold_in / nmfmu_fold_in_block (NMF.transform: new rows folded into a fitted model, every
+                                  iteration of a row in one launch; added at ABI 10, additive);
                                10: nmfmu_plca_normalize / nmfmu_plca_z / nmfmu_plca3 take alpha as double (an argument changed its
                                   type: not additive).  The Dirichlet prior adds fp32(alpha - 1) with the subtraction in double,
                                   as the reference's in-place add does; fp32(alpha) - 1.f was off by 4.7e-5 relative at
@@ -849,6 +851,33 @@ int64_t nmfmu_topk_ws(int n_rows, int k, int nsplit);
 int nmfmu_topk(const float* H, int N, const int32_t* row_ids, int n_rows, const float* W, int C, int rank, int k,
                const int32_t* ex_rowptr, const int32_t* ex_colidx, int nsplit, void* ws, float* out_val, int32_t* out_idx,
                void* stream);
+
+/* ---- fold-in: new rows against a fixed W, all iterations in one launch (additive entries; fold_in.py) ----
+ * The new rows come as CSR (rowptr [n_rows + 1], colidx / vals [nnz], int32 indices below n_cols); H [n_rows][rank] holds the
+ * start H0 on entry and the result on return; W [n_cols][rank] is read only.  Per row, with S its stored columns, max_iter times
+ *   s_j = <h, W[j]>,  h *= ((relu(num) + eps) / (den' + l1 + l2 h))^gamma                                        (nmf.py:78-92)
+ *   NMFMU_FOLD_MISSING, any beta : num = sum_S g_neg(v_j, s_j) W[j], den' = relu(sum_S g_pos(s_j) W[j]) + eps -- g as in
+ *                                  nmfmu_sp_masked_step; aux is not read (may be NULL)
+ *   NMFMU_FOLD_ZERO, beta 1      : num = sum_S v_j / (s_j + eps) W[j], den' = aux[r], the column sums of W as they are
+ *                                  (nmf.py:128-131; nmfmu_rank_sums(W, n_cols, rank, 1, ..))
+ *   NMFMU_FOLD_ZERO, beta 2      : num = sum_S v_j W[j] (formed once), den' = relu(sum_q h[q] aux[q][r]) + eps, aux = W^T W
+ *                                  [rank][rank] (nmfmu_gram)
+ * A row stops after iteration k when max_r |h_k[r] - h_{k-1}[r]| <= tol * max_r h_k[r] (fp32; tol == 0: never) and
+ * n_iter_rows[row] (may be NULL) receives its iteration count.  order (may be NULL): int32 [n_rows], the rows in the order they
+ * are handed out -- longest first balances the launch; it does not change any result.  block / long_rows (0 = default): stored
+ * entries per LDS block (clamped to nmfmu_fold_in_block(rank), what the LDS holds) and the count above which a row takes a whole
+ * workgroup (default nmfmu_fold_in_block(rank): what one wave keeps resident).  A row's result is bitwise independent of block, of order and of the other rows of the call; plain
+ * stores only, no atomics -- a repeated call is bitwise identical.
+ * Null pointers (aux in zero mode included), rank <= 0, n_rows < 0, n_cols <= 0, max_iter < 0, tol < 0, block < 0, long_rows < 0
+ * or an unknown mode: NMFMU_ERR_ARG; rank > 256, or zero mode with beta not in {1, 2}: NMFMU_ERR_UNSUPPORTED; n_rows == 0 or
+ * max_iter == 0: NMFMU_OK without a launch, H untouched -- all before any device work. */
+#define NMFMU_FOLD_MISSING 0
+#define NMFMU_FOLD_ZERO 1
+int nmfmu_fold_in_block(int rank);   /* the default (and largest) block of a rank; 0 outside 1 .. 256 */
+int nmfmu_fold_in(const int32_t* rowptr, const int32_t* colidx, const float* vals, int n_rows, float* H, const float* W,
+                  int n_cols, int rank, float beta, int mode, const float* aux, float l1, float l2, float gamma,
+                  int max_iter, float tol, int32_t* n_iter_rows, const int32_t* order, int block, int long_rows,
+                  void* stream);
 
 /* ---- shift-invariant PLCA (SIPLCA / SIPLCA2 / SIPLCA3, plca.py:376-606) on the NMFD GEMM path ----------------------
  * Same EM update as PLCA with W (C, R, *T), H (B, R, *Lh): factors are addressed [outer][rank][inner], the unscaled

@@ -18,7 +18,8 @@ reference's ``beta_div`` over the stored entries alone, for any beta
 (``nmfmu_sp_masked_loss`` / ``nmfmu_sp_masked_terms``).
 
 ``score_pairs`` / ``topk_scores`` (``scoring.py``) use a fitted model without the ``N x C`` product: its value at
-(row, column) pairs, and the ``k`` best admissible columns per row.
+(row, column) pairs, and the ``k`` best admissible columns per row.  ``fold_in`` (``fold_in.py``) gives ``H`` for rows that
+were not in the training target, with ``W`` fixed.
 """
 from __future__ import annotations
 
@@ -28,9 +29,10 @@ from torch import Tensor
 from . import _capi
 from .sparse_autograd import SparseTarget, sparse_beta_div
 from .scoring import score_pairs, topk_scores
+from .fold_in import fold_in
 
 __all__ = ['kl_div', 'euclidean', 'is_div', 'beta_div', 'sparseness', 'SparseTarget', 'sparse_beta_div', 'score_pairs',
-           'topk_scores']
+           'topk_scores', 'fold_in']
 
 
 def _beta_div_value(input: Tensor, target: Tensor, beta: float) -> Tensor:

@@ -604,6 +604,18 @@ class NMF(BaseComponent):
         from .scoring import topk_scores
         return topk_scores(self.H, self.W, k, rows=rows, exclude=exclude)
 
+    def transform(self, V_new, beta: float = 1, max_iter: int = 200, tol: float = 1e-4, alpha: float = 0,
+                  l1_ratio: float = 0, *, unstored: str = 'zero', H0: Tensor = None, generator=None,
+                  return_n_iter: bool = False):
+        """``H_new [n_new, R]`` for rows that were not in the training target -- a 2-D sparse-COO tensor ``(n_new, C)`` or a
+        ``metrics.SparseTarget`` -- with ``self.W`` fixed: every row iterated on its own, stopped on its own, all in one
+        kernel launch (``fold_in.fold_in``; detached, in the dtype of ``W``).  The module is not modified and ``self.H`` plays
+        no part."""
+        from .fold_in import fold_in
+        assert self.W is not None
+        return fold_in(self.W, V_new, beta, max_iter, tol, alpha, l1_ratio, unstored=unstored, H0=H0, generator=generator,
+                       return_n_iter=return_n_iter)
+
     def _make_engine(self, V, beta, l1, l2, precision, group, allreduce=None):
         from .engine import DenseMU
         assert V.dim() == 2 and V.shape == (self.H.shape[0], self.W.shape[0]), \
