@@ -67,6 +67,8 @@ extern "C" {
                                   pairs and the k best columns per row; added at ABI 10, additive);
                                   nmfmu_fold_in / nmfmu_fold_in_block (NMF.transform: new rows folded into a fitted model, every
                                   iteration of a row in one launch; added at ABI 10, additive);
+                                  nmfmu_hals_sweep (NMF.fit(solver='hals'): the coordinate-descent sweep over the rank for
+                                  beta == 2; added at ABI 10, additive);
                                10: nmfmu_plca_normalize / nmfmu_plca_z / nmfmu_plca3 take alpha as double (an argument changed its
                                   type: not additive).  The Dirichlet prior adds fp32(alpha - 1) with the subtraction in double,
                                   as the reference's in-place add does; fp32(alpha) - 1.f was off by 4.7e-5 relative at
@@ -878,6 +880,26 @@ int nmfmu_fold_in(const int32_t* rowptr, const int32_t* colidx, const float* val
                   int n_cols, int rank, float beta, int mode, const float* aux, float l1, float l2, float gamma,
                   int max_iter, float tol, int32_t* n_iter_rows, const int32_t* order, int block, int long_rows,
                   void* stream);
+
+/* ---- HALS: coordinate descent for beta == 2 (additive entry; hals.py) ---------------------------------
+ * nmfmu_hals_sweep: one Gauss-Seidel pass over the rank on f [rows][rank], in place, every row on its own.  With
+ * a [rows][lda] = X_owner @ panel (lda >= rank elements per row: nmfmu_sp_partial writes r_pad, nmfmu_reconstruct_backward
+ * rank) and gram [rank][rank] = panel^T panel (nmfmu_gram), for r = 0 .. rank-1 in this order
+ *   s         = sum_{j != r} f[row][j] gram[j][r]                  (j < r: the values this pass already wrote)
+ *   f[row][r] = max(eps, ((a[row][r] - l1) - s) / ((gram[r][r] + l2) + eps)),   eps = 2^-23
+ * -- the exact minimiser of 1/2 |X - owner panel^T|^2 + l1 sum f + l2/2 |f|^2 along the coordinate, floored at eps (not 0:
+ * a factor can be handed on to the multiplicative update, which never leaves an exact zero); the eps in the denominator
+ * covers a panel column that is all floor.  gram must be SYMMETRIC (a Gram matrix is, and nmfmu_gram writes it so bit for
+ * bit): coordinate r reads its row r.
+ * Arithmetic: fp32; term j of s goes to accumulator j mod 4 by fused multiply-add in increasing j (the own term as an exact
+ * +0), s = (acc0 + acc1) + (acc2 + acc3).  One lane per row, one 64-lane workgroup per 64 rows with the rows in LDS: a row's
+ * bits depend on that row of f and a, on gram, l1 and l2 alone -- not on rows, the launch geometry or the other rows; plain
+ * vector stores, no atomics: a repeated call is bitwise identical.  a and gram are only read; of f only [rows][rank] is
+ * written.
+ * Null pointers, rows <= 0, rank <= 0, lda < rank: NMFMU_ERR_ARG; rank > 256: NMFMU_ERR_UNSUPPORTED -- both before any
+ * device work. */
+int nmfmu_hals_sweep(float* f, int rows, int rank, const float* a, int64_t lda, const float* gram, float l1, float l2,
+                     void* stream);
 
 /* ---- shift-invariant PLCA (SIPLCA / SIPLCA2 / SIPLCA3, plca.py:376-606) on the NMFD GEMM path ----------------------
  * Same EM update as PLCA with W (C, R, *T), H (B, R, *Lh): factors are addressed [outer][rank][inner], the unscaled

@@ -380,7 +380,7 @@ class BaseComponent(nn.Module):
     @torch.no_grad()
     def fit(self, V: Tensor, beta: float = 1, tol: float = 1e-4, max_iter: int = 200, verbose: bool = False,
             alpha: float = 0, l1_ratio: float = 0, *, precision: Optional[str] = None, process_group=None,
-            allreduce: Optional[str] = None, unstored: str = 'zero') -> int:
+            allreduce: Optional[str] = None, unstored: str = 'zero', solver: str = 'mu') -> int:
         """Minimise the beta-divergence between ``V`` and the model by multiplicative updates.
 
         Same contract as the reference (nmf.py:297-409): W half-step, then H
@@ -419,7 +419,30 @@ class BaseComponent(nn.Module):
                          the stored set, O(nnz * rank) for every beta; beta <= 0 is admitted when the stored values are
                          strictly positive.  Exact fp32: ``precision`` is ignored and ``last_precision`` is 'fp32'.  A dense
                          target with a mask goes in as ``V.sparse_mask(mask)``.  NMF only, not sharded.
+          solver         'mu' (default): the multiplicative update.  'hals': cyclic coordinate descent (Cichocki & Phan 2009;
+                         sklearn's default solver) for beta == 2 -- the same ``X @ panel`` and Gram matrix as a beta = 2 MU
+                         half-step, then one Gauss-Seidel sweep over the rank per row (``hals.hals_sweep``): a few
+                         iterations reach the loss MU needs hundreds for.  The factors are first scaled by the scalar that
+                         minimises the loss and floored at eps (``hals.HalsEngine``); entries never fall below eps, so an MU
+                         fit can continue from the result.  Loss, stop rule and return value as above; alpha / l1_ratio
+                         penalise as in the MU denominators.  Dense and sparse-COO (unstored='zero') targets, NMF only,
+                         rank <= 256, not sharded.  Exact fp32: ``precision`` is ignored and ``last_precision`` is 'fp32'.
         """
+        if solver not in ('mu', 'hals'):
+            raise ValueError(f"solver must be 'mu' or 'hals', got {solver!r}")
+        if solver == 'hals':
+            if float(beta) != 2.0:
+                raise NotImplementedError(f"solver='hals': the coordinate minimiser is closed-form only for beta = 2, got "
+                                          f"beta = {beta:g}")
+            if not isinstance(self, NMF):
+                raise NotImplementedError(f"solver='hals' is implemented for NMF only, not {type(self).__name__}")
+            if unstored == 'missing':
+                raise NotImplementedError("solver='hals': the Gram shortcut needs unstored = 'zero' (with unstored='missing' "
+                                          "the denominator runs over the stored entries only)")
+            if process_group is not None:
+                raise NotImplementedError("solver='hals' is not sharded (process_group must be None)")
+            if self.W is not None and self.W.shape[1] > 256:
+                raise NotImplementedError(f"solver='hals': rank {self.W.shape[1]} > 256, the limit of the sparse kernels")
         if unstored not in ('zero', 'missing'):
             raise ValueError(f"unstored must be 'zero' or 'missing', got {unstored!r}")
         if unstored == 'missing':
@@ -446,7 +469,7 @@ class BaseComponent(nn.Module):
             W.data, H.data = W.data.float().contiguous(), H.data.float().contiguous()
             try:
                 return self.fit(V, beta, tol, max_iter, verbose, alpha, l1_ratio, precision=precision,
-                                process_group=process_group, allreduce=allreduce, unstored=unstored)
+                                process_group=process_group, allreduce=allreduce, unstored=unstored, solver=solver)
             finally:
                 w32, h32 = W.data, H.data
                 W.data, H.data = keep
@@ -460,7 +483,12 @@ class BaseComponent(nn.Module):
         V = V.detach()
         if V.dtype != torch.float32:
             V = V.float()
-        if sparse:
+        if solver == 'hals':
+            from .hals import HalsEngine
+            if not (W.data.is_contiguous() and H.data.is_contiguous()):
+                W.data, H.data = W.data.contiguous(), H.data.contiguous()
+            eng = HalsEngine(V, W.data, H.data, l1, l2, update_W=W.requires_grad, update_H=H.requires_grad)
+        elif sparse:
             if process_group is not None:
                 raise NotImplementedError('sparse targets are not sharded')
             from .sparse_engine import MaskedMU, SparseMU
