@@ -705,3 +705,417 @@ XB_CLAIMS = {'ring_prologue_short': (3, 4), 'ring_rem1': (3, 4), 'ring_rem2': (3
              'den_tiles_shared': (3, 4), 'den_tiles_fewer_splits_than_tiles': (3, 4), 'den_one_slab_unsplit': (4,),
              'empty_split': (3, 4), 'empty_split_owns_den_tile': (4,), 'short_last_split': (3, 4), 'fused_apply': (3, 4), 'ragged_m': (3, 4), 'ragged_k': (3, 4),
              'ragged_r': (3, 4), 'm1': (3, 4)}
+
+
+# ---- the dense loss pass (kModeLoss of fused_kernel / pp_kernel), the riding loss, metrics.beta_div -----------------------
+# What ``DenseMU.divergence()`` and fit()'s stop rule read.  One workgroup per (row block mb, contraction split ks) writes ONE
+# float into loss_part[mb * nsplit + ks] (nmfmu_fused.h:907-914 on four waves, nmfmu_pp.h:818-825 on eight); the fixed-order
+# sum_finalize_kernel (nmfmu_aux.hip:403-414) adds them in float64.  The model below gives every partial in float64 from the
+# operand images the GPU holds, and a bound of its own:
+#
+#     |got - ref|  <=  sum over the workgroup's elements i of
+#                          U * sum_k c_k |term_k(i)|                  loss_elem's own roundings           (``c_elem``)
+#                        + gamma(depth_i) * |l_i|                     the fp32 additions element i passes (``n_chain``, ``tree``)
+#                        + gamma(n_seq_S) * |dl/ds (i)| s_i           the fp32 reconstruction              (``err_S``)
+#
+# with U = 2^-24 and gamma(n) = n U / (1 - n U).  It is the form  U (c_elem + n_chain + tree) sum|terms| + sum |dl/ds| |s|
+# err_S  with two replacements that only tighten it: the summation error is taken on |l_i| <= sum_k |term_k(i)|, and element
+# i is charged the additions it really passes through, depth_i <= n_chain + tree, not the longest chain.  Every constant is
+# counted from the source; none comes from running a kernel.
+#
+# * c_elem, from loss_elem (nmfmu_fused.h:333-352); a hardware transcendental (v_log_f32, v_exp_f32, v_rcp_f32: one ulp)
+#   counts as LOSS_FN = 2 roundings of its own result, the rounded constant kLn2 as one:
+#     beta 2   d = s - x, 0.5 d d: d enters twice, one multiply (x 0.5 is exact)                           c = 3 on d^2 / 2
+#     beta 1   x ((lx - ls) kLn2) - x + (s - eps), terms x ln(x + eps), x ln s, x, s:
+#              the logarithm 2, lx - ls 1, x kLn2 2, x x 1, the two additions that follow 1 each            c = 8 on the two x ln
+#              x + eps rounds once: ln(x + eps) moves by U, x ln(x + eps) by U |x|; two additions            c = 3 on x
+#              s - eps, the last addition                                                                   c = 2 on s
+#     beta 0   xe / s - (lx - ls) kLn2 - 1, xe = x + eps, terms xe / s, ln xe, ln s, 1:
+#              xe 1, v_rcp 2, the multiply 1, two subtractions                                              c = 6 on xe / s
+#              the logarithm 2, lx - ls 1, x kLn2 2, two subtractions                                       c = 7 on the two ln
+#              xe's rounding moves ln xe by U; the last subtraction                                         c = 2 on the 1
+#     generic  (t1 + (beta - 1) t2 - beta xb sb1) / (beta (beta - 1)), t1 = exp2(beta log2 xb), sb1 = exp2((beta - 1) log2 s),
+#              t2 = sb1 s.  An exponent e = c log2 v carries (2 + 1 [+ 1 where c = beta - 1 is itself rounded]) U |e| and
+#              moves exp2 by ln 2 times that; exp2's own ulp 2.  The quotient: beta - 1, the product, the division (one ulp)
+#              = 4; the two additions 1 each where a term passes them.
+#              t1:  2 + 3 |beta ln xb| + |beta| (xb = x + eps rounds, beta < 0) + 2 + 4
+#              t2:  2 + 4 |(beta - 1) ln s| + 3 (x s, x (beta - 1), beta - 1) + 2 + 4
+#              t3:  2 + 4 |(beta - 1) ln s| + 3 (two multiplies, xb) + 1 + 4
+#              less every operation on the scalar beta that is exact in fp32 for the beta at hand (``_gen_roundings``:
+#              beta - 1.f for 0.5, 1.5, 3 and -1, a multiplication by a power of two)
+#   Contraction to fused multiply-adds (hipcc's default) only removes roundings.
+# * n_chain: a lane adds its 32 elements of every tile to ONE accumulator in the order (tt, d, low / high half of the word)
+#   (``elem_pair`` through ``elementwise``, nmfmu_fused.h:658-663, :703-707; nmfmu_pp.h:572-589), masked elements as 0.f:
+#   32 x (tiles of the split) additions, element i at slot 32 (t - t0) + (k mod 32) passes the 32 nt - slot that follow.
+# * tree: six __shfl_xor levels, then (r0 + r1) + (r2 + r3): 6 + 2 = 8 on four waves, 6 + 3 = 9 on eight.
+# * err_S: products of two 16-bit operands are exact in fp32 and all non-negative; a product passes through at most the 16
+#   additions inside its MFMA (K = 16; the order is not documented, the worst is taken, as ``gram_plan`` does) and one per
+#   MFMA of the chain that follows, R_PAD / 16 of them (three times as many with the lo planes of bf16x3), eps being the
+#   seed: n_seq_S = 16 + planes R_PAD / 16 + 1.  The lo x lo product bf16x3 never forms is left out of the float64 S too
+#   (``_gemm``), so it needs no allowance; the ping-pong kernel's 2^23 scaling of bf16 is exact.
+#   |dl/ds| s:  beta 2: |s - x| s;  beta 1: |s - x|;  beta 0: |1 - xe / s|;  generic: |s^beta - xb s^(beta - 1)|.
+# A partial whose bound is zero (an empty split, a split or a row block of padding only) must be exactly 0.0.
+LOSS_U = 2.0 ** -24
+LOSS_FN = 2.0                 # roundings' worth of a one-ulp hardware transcendental
+LOSS_TREE = {'fused': 6 + 2, 'pp': 6 + 3}
+LOSS_CAP = 1e-5               # non-vacuity: a case's bound may not exceed this fraction of the partial's sum |terms|
+LN2 = float(np.log(2.0))
+
+
+def _gamma(n):
+    n = np.asarray(n, dtype=np.float64)
+    return n * LOSS_U / (1.0 - n * LOSS_U)
+
+
+def s_chain(r_pad: int, precision: str) -> int:
+    """n_seq_S: the longest chain of fp32 additions behind one element of S = owner panel^T + eps (see above)."""
+    return 16 + (3 if precision == 'bf16x3' else 1) * (r_pad // 16) + 1
+
+
+def loss_elem_terms(s, x, beta: float, eps_in_log=True):
+    """loss_elem in float64, term by term as the source forms them.  ``s`` already holds eps (none at beta == 2).
+    Returns (l, w, sens): the element's loss, sum_k c_k |term_k| (in units of U) and |dl/ds| s."""
+    s = np.asarray(s, dtype=np.float64)
+    x = np.asarray(x, dtype=np.float64)
+    beta = float(np.float32(beta))
+    kind = beta_kind(beta)
+    le = EPS if eps_in_log else 0.0
+    with np.errstate(divide='ignore', invalid='ignore', over='ignore'):
+        if kind == 'euc':
+            d = s - x
+            l = 0.5 * d * d
+            return l, 3.0 * np.abs(l), np.abs(d) * np.abs(s)
+        if kind == 'kl':
+            a1, a2 = x * np.log(x + le), x * np.log(s)
+            l = (a1 - a2) - x + (s - EPS)
+            w = (2 * LOSS_FN + 4) * (np.abs(a1) + np.abs(a2)) + 3.0 * np.abs(x) + 2.0 * np.abs(s)
+            return l, w, np.abs(s - x)
+        if kind == 'is':
+            xe = x + EPS
+            q, lx, ls = xe / s, np.log(x + le), np.log(s)
+            l = q - (lx - ls) - 1.0
+            w = (LOSS_FN + 4) * np.abs(q) + (LOSS_FN + 5) * (np.abs(lx) + np.abs(ls)) + 2.0
+            return l, w, np.abs(1.0 - q)
+        # generic branch (0.5 and 1.5 take it too in loss mode: nmfmu_fused.h:659)
+        xb = x + EPS if beta < 0 else x
+        pos = xb > 0
+        xs = np.where(pos, xb, 1.0)
+        t1 = np.where(pos, np.power(xs, beta), 0.0)
+        sb1 = np.power(s, beta - 1.0)
+        t2 = sb1 * s
+        den = beta * (beta - 1.0)
+        T1, T2, T3 = t1 / den, (beta - 1.0) * t2 / den, -beta * xb * sb1 / den
+        l = T1 + T2 + T3
+        ex_x = np.abs(beta * np.log(xs))
+        ex_s = np.abs((beta - 1.0) * np.log(s))
+        r = _gen_roundings(beta)
+        w = ((LOSS_FN + (LOSS_FN + r['mul_b']) * ex_x + (abs(beta) if beta < 0 else 0.0) + 2 + r['quot']) * np.abs(T1)
+             + (LOSS_FN + (LOSS_FN + r['mul_bm1'] + r['bm1']) * ex_s + 1 + r['mul_bm1'] + r['bm1'] + 2 + r['quot']) * np.abs(T2)
+             + (LOSS_FN + (LOSS_FN + r['mul_bm1'] + r['bm1']) * ex_s + r['mul_b'] + 1 + (1 if beta < 0 else 0) + 1 + r['quot'])
+             * np.abs(T3))
+        return l, w, np.abs(t2 - xb * sb1)
+
+
+def _gen_roundings(beta: float) -> dict:
+    """Which fp32 operations on the scalar beta round at all (counted, 0 or 1 each): beta - 1.f (exact for 0.5, 1.5, 3, -1, not
+    for 0.3f), a multiplication by beta or by beta - 1 (exact where that is a power of two), and the quotient's
+    beta * (beta - 1.f) plus its division (one ulp = 2)."""
+    b = np.float32(beta)
+    bm1 = np.float32(b - np.float32(1.0))
+    r_bm1 = 0 if float(bm1) == float(b) - 1.0 else 1
+    pow2 = lambda v: float(np.frexp(abs(float(v)))[0]) == 0.5
+    r_prod = 0 if float(np.float32(b * bm1)) == float(b) * float(bm1) else 1
+    return dict(bm1=r_bm1, mul_b=0 if pow2(b) else 1, mul_bm1=0 if pow2(bm1) else 1, quot=r_bm1 + r_prod + LOSS_FN)
+
+
+def loss_abs_terms(s, x, beta: float):
+    """sum_k |term_k| of an element (beta == 1: |x ln(x + eps)| + |x ln s| + |x| + |s|)."""
+    s = np.asarray(s, dtype=np.float64)
+    x = np.asarray(x, dtype=np.float64)
+    beta = float(np.float32(beta))
+    kind = beta_kind(beta)
+    if kind == 'euc':
+        return 0.5 * (np.abs(s) + np.abs(x)) ** 2      # d = s - x is formed first: |s| + |x| is what its roundings scale with
+    if kind == 'kl':
+        return np.abs(x * np.log(x + EPS)) + np.abs(x * np.log(s)) + np.abs(x) + np.abs(s)
+    if kind == 'is':
+        return np.abs((x + EPS) / s) + np.abs(np.log(x + EPS)) + np.abs(np.log(s)) + 1.0
+    xb = x + EPS if beta < 0 else x
+    t1 = np.where(xb > 0, np.power(np.where(xb > 0, xb, 1.0), beta), 0.0)
+    sb1 = np.power(s, beta - 1.0)
+    den = abs(beta * (beta - 1.0))
+    return (np.abs(t1) + np.abs((beta - 1.0) * sb1 * s) + np.abs(beta * xb * sb1)) / den
+
+
+def loss_plan(N: int, C: int, R: int, precision: str, beta: float, ncu: int, nsplit=None, block_rows=None, gram=False):
+    """What the loss pass of a DenseMU runs with.  It is launched on ``step_h`` (owner H, contraction over C), so tile height
+    and nsplit are those the MU step's family chose; the kernel is pp on 256-row tiles and the four-wave kernel otherwise
+    (sp, sp2 and xb have no loss instance: fused_dispatch tests ``mode == kModeMU`` for them, nmfmu_capi.hip:171-183).
+    The loss-mode tile rule: tiles_per_split = ceil(ktiles / nsplit), rounded up to even on pp ONLY (nmfmu_capi.hip:124,
+    :162) -- not to the four of sp / sp2 -- so ``tiles`` differs from ``mu_tiles`` exactly where the MU family is sp / sp2
+    and ceil(ktiles / nsplit) is no multiple of four."""
+    p = half_step_plan(N, C, R, precision, beta, ncu, nsplit, block_rows, gram)['h']
+    fam = 'pp' if p['block_rows'] == 256 else 'fused'
+    tiles = split_tiles(p['k_pad'], p['nsplit'], fam)
+    return dict(M=N, K=C, R=R, m_pad=p['m_pad'], k_pad=p['k_pad'], r_pad=p['r_pad'], block_rows=p['block_rows'], family=fam,
+                nsplit=p['nsplit'], tiles=tiles, tps=tiles_per_split(p['k_pad'], p['nsplit'], fam)[1],
+                mu_family=p['family'], mu_tiles=p['tiles'], nparts=(p['m_pad'] // p['block_rows']) * p['nsplit'],
+                tree=LOSS_TREE[fam], s_seq=s_chain(p['r_pad'], precision))
+
+
+def _padded(a, rows, cols):
+    out = np.zeros((rows, cols), dtype=np.float64)
+    a = np.asarray(a, dtype=np.float64)
+    out[:a.shape[0], :a.shape[1]] = a
+    return out
+
+
+def _recon(A_img, B_img, m_pad, k_pad, seed):
+    """A B^T + seed on the padded grid (padded rows of an image are zero: S = seed there)."""
+    rk = max(A_img[0].shape[1], B_img[0].shape[1])
+    pa = [_padded(a, m_pad, rk) for a in A_img if a is not None]
+    pb = [_padded(b, k_pad, rk) for b in B_img if b is not None]
+    return _gemm(pa, pb[0].T, pb[1].T if len(pb) == 2 else None) + seed
+
+
+def loss_partials(X, A_img, B_img, beta: float, precision: str, plan: dict, *, rounding=True, x_stored=None,
+                  col_mask=True, m_valid=None, eps_in_log=True, tiles=None):
+    """Every partial of the loss pass, float64.  X: [M, K] fp32 target; A_img / B_img = (hi, lo or None) image values of the
+    owner (H) and the panel (W), [>= M, >= R] / [>= K, >= R] (the GPU test passes the images read back, padding included;
+    rounding=False: the exact factors, an exact target).  Seeded faults: ``col_mask=False`` (the ``k0 < a.K`` test dropped),
+    ``m_valid`` (another row count in ``m0 < a.M``), ``eps_in_log=False`` (log(x) for log(x + eps)), ``tiles`` (another tile
+    list than the plan's).  Returns a dict of arrays [nparts] -- ref, bound, abs_terms -- and n_chain [nparts]: the element
+    count of the longest per-lane chain (32 per tile)."""
+    M, K, m_pad, k_pad, br, ns = plan['M'], plan['K'], plan['m_pad'], plan['k_pad'], plan['block_rows'], plan['nsplit']
+    kind = beta_kind(beta)
+    if rounding:
+        x = stored_target(X, precision).reshape(np.asarray(X).shape) if x_stored is None else np.asarray(x_stored, np.float64)
+    else:
+        x = np.asarray(X, dtype=np.float64)
+    xp = _padded(x, m_pad, k_pad)
+    S = _recon(A_img, B_img, m_pad, k_pad, 0.0 if kind == 'euc' else EPS)
+    l, w, sens = loss_elem_terms(S, xp, beta, eps_in_log)
+    at = loss_abs_terms(S, xp, beta)
+    mv = M if m_valid is None else m_valid
+    ok = (np.arange(m_pad)[:, None] < mv) & ((np.arange(k_pad)[None, :] < K) | (not col_mask))
+    tl = plan['tiles'] if tiles is None else tiles
+    tps = plan['tps']
+    nparts = plan['nparts']
+    ref, bound, abs_terms = np.zeros(nparts), np.zeros(nparts), np.zeros(nparts)
+    n_chain = np.zeros(nparts, dtype=np.int64)
+    cols = np.arange(k_pad)
+    for mb in range(m_pad // br):
+        rows = slice(mb * br, (mb + 1) * br)
+        for ks in range(ns):
+            nt = tl[ks]
+            i = mb * ns + ks
+            n_chain[i] = 32 * nt
+            if nt == 0:
+                continue
+            t0 = ks * tps
+            c = slice(t0 * KBK, (t0 + nt) * KBK)
+            m = ok[rows, c]
+            depth = 32 * nt - (32 * (cols[c] // KBK - t0) + cols[c] % 32) + plan['tree']
+            lv = np.where(m, l[rows, c], 0.0)
+            ref[i] = lv.sum()
+            if rounding:
+                e = LOSS_U * w[rows, c] + _gamma(depth)[None, :] * (np.abs(lv) + LOSS_U * w[rows, c]) \
+                    + _gamma(plan['s_seq']) * sens[rows, c]
+                abs_terms[i] = np.where(m, at[rows, c], 0.0).sum()
+                bound[i] = np.where(m, e, 0.0).sum() + 2.0 ** -50 * abs_terms[i]
+    return dict(ref=ref, bound=bound, abs_terms=abs_terms, n_chain=n_chain)
+
+
+def partial_excess(got, ref, bound) -> np.ndarray:
+    """Per partial |got - ref| / bound; a partial whose bound is zero must equal its reference (0.0) exactly; a value that
+    is not finite counts as inf.  The check is ``partial_excess(...).max() <= 1``."""
+    got = np.asarray(got, dtype=np.float64)
+    ref = np.asarray(ref, dtype=np.float64)
+    bound = np.asarray(bound, dtype=np.float64)
+    diff = np.abs(got - ref)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        r = np.where(bound > 0, diff / np.where(bound > 0, bound, 1.0), np.where(diff == 0, 0.0, np.inf))
+    return np.where(np.isfinite(got), r, np.inf)
+
+
+# The riding loss (PPCfg::LACC, nmfmu_pp.h:91-97): the W half-step that follows a checkpoint (owner W, contraction over N)
+# accumulates, per lane, four chains of  la += x log2 s  (ONE fused multiply-add: the product is not rounded) and of
+# ls += s over EVERY element of its tiles, padding included (x = 0, s = eps there): elements 2d .. 2d + 3 of S^T tile tt go to
+# chains 0 .. 3 (:618-636, :687-704), eight elements per chain and tile; then (la0 + la1) + (la2 + la3), six __shfl_xor levels
+# (:804-808), one pair per wave at [16 wg + 2 wave].  Wave w owns the rows 256 mb + 32 w .. + 31 and all tiles of the split.
+# x is the stored target (the fp16 half of the word, or the 24-bit value of 'f16r').
+#   la: the logarithm 2 U |x log2 s|; element i passes 8 nt - slot additions of its chain, 2 + 6 after it; S moves
+#       x log2 s by gamma(n_seq_S) |x| / ln 2.
+#   ls: the additions alike; S itself gamma(n_seq_S) s.
+RIDING_TREE = 2 + 6
+
+
+def riding_plan(N: int, C: int, R: int, precision: str, ncu: int, nsplit=None):
+    p = half_step_plan(N, C, R, precision, 1.0, ncu, nsplit, None)['w']
+    assert p['family'] == 'pp' and precision in ('f16', 'f16r')
+    tps = tiles_per_split(p['k_pad'], p['nsplit'], 'pp')[1]
+    return dict(M=C, K=N, R=R, m_pad=p['m_pad'], k_pad=p['k_pad'], r_pad=p['r_pad'], nsplit=p['nsplit'], tiles=p['tiles'],
+                tps=tps, nwg=(p['m_pad'] // 256) * p['nsplit'], s_seq=s_chain(p['r_pad'], precision),
+                n_all=p['m_pad'] * p['k_pad'])
+
+
+def riding_partials(Xt, A_img, B_img, precision: str, plan: dict, x_stored=None):
+    """The 8 pairs per workgroup, float64: ref [nwg, 8, 2] = (sum x log2 s, sum s) and bound [nwg, 8, 2].  Xt: [C, N] fp32 (the
+    target transposed: the W half-step's rows are columns of V); A_img / B_img: image values of W and of H BEFORE the update."""
+    m_pad, k_pad, ns, tps = plan['m_pad'], plan['k_pad'], plan['nsplit'], plan['tps']
+    x = stored_target(Xt, precision).reshape(np.asarray(Xt).shape) if x_stored is None else np.asarray(x_stored, np.float64)
+    xp = _padded(x, m_pad, k_pad)
+    S = _recon((A_img[0], None), (B_img[0], None), m_pad, k_pad, EPS)
+    xl = xp * np.log2(S)
+    ref = np.zeros((plan['nwg'], 8, 2))
+    bound = np.zeros((plan['nwg'], 8, 2))
+    cols = np.arange(k_pad)
+    gs = _gamma(plan['s_seq'])
+    for mb in range(m_pad // 256):
+        for ks in range(ns):
+            nt = plan['tiles'][ks]
+            if nt == 0:
+                continue
+            t0 = ks * tps
+            c = slice(t0 * KBK, (t0 + nt) * KBK)
+            kk = cols[c] % 32                                     # 16 tt + e
+            slot = 8 * (cols[c] // KBK - t0) + 4 * (kk // 16) + (kk % 16) // 4
+            depth = _gamma(8 * nt - slot + RIDING_TREE)[None, :]
+            for wv in range(8):
+                r = slice(mb * 256 + 32 * wv, mb * 256 + 32 * wv + 32)
+                i = mb * ns + ks
+                ref[i, wv, 0] = xl[r, c].sum()
+                ref[i, wv, 1] = S[r, c].sum()
+                bound[i, wv, 0] = ((LOSS_FN * LOSS_U + depth) * np.abs(xl[r, c]) + gs * np.abs(xp[r, c]) / LN2).sum() \
+                    + 2.0 ** -50 * np.abs(xl[r, c]).sum()
+                bound[i, wv, 1] = ((depth + gs) * S[r, c]).sum()
+    return dict(ref=ref, bound=bound)
+
+
+def riding_total(V, A_img, B_img, precision: str, plan: dict, x_stored=None, n_all=None):
+    """(ref, bound) of the value riding_finish_kernel leaves (nmfmu_aux.hip:520-538): ref = the float64 KL of metrics.py:22
+    between the fp32 target V [N, C] and the reconstruction of the images.  The kernel's value is
+        A - ln 2 sum x' log2 s - C + (sum s - n_all eps)
+    A = sum x ln(x + eps) and C = sum x from target_sums_kernel on the fp32 target (per element in fp32: x + eps moves the
+    term by U |x|, the logarithm 2, x kLn2 2, x x 1; summed in float64), the two sums from the pairs (``riding_partials``),
+    x' the STORED target.  sum s runs over all n_all = m_pad k_pad processed elements, each padded one exactly eps (its fp32
+    accumulator is the seed), so sum s - n_all eps = sum over the valid elements of (s - eps).  x' != x moves the value by
+    sum (x - x') ln s exactly: allowed as sum |x - x'| |ln s| from the data (<= 2^-17 sum |x ln s| for 'f16r'; zero for an
+    fp16-exact target in 'f16').  ``n_all``: seeded fault (another count than the plan's)."""
+    V = np.asarray(V, dtype=np.float64)
+    Xt = V.T
+    M, K = plan['M'], plan['K']
+    xs = stored_target(Xt, precision).reshape(Xt.shape) if x_stored is None else np.asarray(x_stored, np.float64)
+    S = _recon((A_img[0], None), (B_img[0], None), plan['m_pad'], plan['k_pad'], EPS)[:M, :K]
+    a = Xt * np.log(Xt + EPS)
+    ref = float((a - Xt * np.log(S) - Xt + (S - EPS)).sum())
+    rp = riding_partials(Xt, A_img, B_img, precision, plan, x_stored=xs)
+    bound = float(LOSS_U * (5.0 * np.abs(a) + np.abs(Xt)).sum() + LN2 * rp['bound'][..., 0].sum() + rp['bound'][..., 1].sum()
+                  + (np.abs(Xt - xs) * np.abs(np.log(S))).sum()
+                  + 2.0 ** -50 * (np.abs(a).sum() + np.abs(Xt).sum() + LN2 * np.abs(rp['ref'][..., 0]).sum()
+                                  + rp['ref'][..., 1].sum()))
+    kernel_value = float(a.sum() - LN2 * rp['ref'][..., 0].sum() - Xt.sum()
+                         + (rp['ref'][..., 1].sum() - (plan['n_all'] if n_all is None else n_all) * EPS))
+    return dict(ref=ref, bound=bound, kernel_value=kernel_value)
+
+
+def beta_div_bound(x, y, beta: float):
+    """(ref, bound) of metrics.beta_div(x, y, beta) on plain arrays (beta_div_kernel, nmfmu_aux.hip:558-572): s = x + eps is
+    one fp32 addition (none at beta == 2), loss_elem runs in fp32 (``loss_elem_terms``' weights), the sum in float64, the
+    result is rounded to fp32 once.  ref is the float64 sum of the same elements."""
+    x = np.asarray(x, dtype=np.float64).reshape(-1)
+    y = np.asarray(y, dtype=np.float64).reshape(-1)
+    s = x if beta_kind(beta) == 'euc' else x + EPS
+    l, w, sens = loss_elem_terms(s, y, beta)
+    ref = float(l.sum())
+    at = float(loss_abs_terms(s, y, beta).sum())
+    return ref, float(LOSS_U * (w + sens).sum() + LOSS_U * abs(ref) + 2.0 ** -50 * at)
+
+
+def loss_cases(ncu: int):
+    """The case matrix of tests/test_gpu_loss_emulated_parity.py: dicts like ``parity_cases`` plus ``gram`` (the engine is
+    built with allow_gram) and ``fitted`` (V = fp32(H0 W0^T): the loss cancels completely)."""
+    cases = []
+
+    def add(group, prec, beta, N, C, R, nsplit=None, block_rows=None, stage='dma', target='rand', gram=False, fitted=False):
+        tag = f'{group}-{prec}-b{beta:g}-{N}x{C}r{R}-ns{nsplit}' + (f'-{target}' if target != 'rand' else '') \
+            + ('-fitted' if fitted else '')
+        cases.append(dict(id=tag, group=group, family=group, precision=prec, beta=float(beta), N=N, C=C, R=R, nsplit=nsplit,
+                          block_rows=block_rows, stage=stage, target=target, gram=gram, fitted=fitted))
+
+    # ping-pong loss kernel
+    for prec in ('bf16', 'f16', 'f16r'):
+        add('pp', prec, 1, 1, 300, 1, 1)
+        add('pp', prec, 1, 257, 1100, 33, 4)                # [6, 6, 6, 2]: odd raw tiles per split; the last split is padding only
+        add('pp', prec, 1, 300, 2100, 128, None)
+        add('pp', prec, 1, 300, 1000, 64, 2, target='zeros')
+    add('pp', 'f16', 1, 257, 1700, 33, 6)                   # [6, 6, 6, 6, 4, 0]: an empty loss split
+    # four-wave loss kernel: the shape rotation of ``parity_cases``; a case whose bound exceeds LOSS_CAP of sum |terms| takes the
+    # shape's shortened contraction (LOSS_SHAPES), beta == 3 the shortest one throughout
+    i = 0
+    for beta in (1.0, 0.0, 0.5, 1.5, 0.3, 3.0, -1.0, 2.0):
+        for prec in PRECISIONS:
+            if prec == 'f16r' and beta == 2.0:
+                continue
+            for _ in range(len(LOSS_SHAPES)):
+                k = i % len(LOSS_SHAPES)
+                i += 1
+                if not (prec == 'bf16x3' and pad_rank(LOSS_SHAPES[k][0][2]) > 128):
+                    break
+            if beta == 3.0:
+                k = 0
+            full, ns, short, short_betas = LOSS_SHAPES[k]
+            N, C, R = short if beta in short_betas else full
+            add('fused', prec, beta, N, C, R, ns, block_rows=128 if beta == 1.0 else None)
+    for beta in (1.0, 0.5, 2.0):
+        for prec in ('f16', 'bf16x3'):
+            add('fused', prec, beta, 200, 330, 24, None, block_rows=128 if beta == 1.0 else None, target='zeros')
+    add('fused', 'f16x', 1.0, 200, 330, 24, None, block_rows=128, target='zero_row')
+    add('fused', 'bf16', 0.5, 100, 2304, 24, 7)             # [6] * 6 + [0]: an empty loss split, and a row block of padding only
+    # the MU step is not the four-wave kernel, the loss is
+    add('sp', 'f16', 1, 300, 1200, 256, 4, stage='nop2')    # MU [8, 8, 4, 0], loss [5, 5, 5, 5]
+    add('sp', 'f16', 1, 300, 200, 200, None)                # MU [4], loss [4]
+    for beta in (0.5, 0.0):
+        add('sp2', 'f16', beta, 300, 1200, 100, 4)          # MU [8, 8, 4, 0], loss [5, 5, 5, 5]
+    for prec in ('f16', 'f16x'):
+        add('xb', prec, 2, 384, 700, 64, 3, gram=True)      # MU [4, 4, 4] = loss (1100 columns, [7, 7, 6], exceed the cap)
+    # a fitted state: the loss cancels completely
+    add('pp', 'f16r', 1, 257, 1100, 33, 4, fitted=True)
+    add('fused', 'f16x', 2, 384, 700, 64, 3, fitted=True)
+    return cases
+
+
+# shapes of the four-wave rotation -- ``parity_cases``' four: (N, C, R), forced split, the same with a contraction short enough
+# for LOSS_CAP (four tiles per split), and the betas that need it (tests/test_mu_emulation.py computes the cap for every case)
+LOSS_SHAPES = [((200, 330, 24), None, (200, 250, 24), (3.0,)),
+               ((384, 1100, 64), 3, (384, 700, 64), (1.5, 3.0, 2.0)),
+               ((520, 700, 100), 1, (520, 250, 100), (1.0, 0.5, 1.5, 3.0, -1.0, 2.0)),
+               ((300, 640, 200), 2, (300, 500, 200), (1.5, 3.0, 2.0))]
+
+
+def loss_problem(case):
+    """(V, W0, H0) of a loss case: ``make_problem``'s, or the fitted state V = fp32(H0 W0^T) on its factors."""
+    V, W0, H0 = make_problem(case)
+    if case.get('fitted'):
+        V = (H0.double() @ W0.double().t()).float()
+    return V, W0, H0
+
+
+RIDING_CASES = [dict(id=f'{prec}-{N}x{C}r{R}-ns{ns}' + (f'-{target}' if target != 'rand' else ''), precision=prec, beta=1.0, N=N,
+                     C=C, R=R, nsplit=ns, target=target, family='pp')
+                for prec in ('f16', 'f16r')
+                for (N, C, R, ns, target) in ((257, 1100, 33, 4, 'rand'), (300, 1000, 64, None, 'zeros'), (1, 300, 1, None, 'rand'))]
+
+
+def riding_problem(case):
+    """``make_problem``'s data; precision 'f16' is specified for targets fp16 holds exactly (DenseMU's admission test), so its
+    target is rounded to fp16 once here -- zeros stay zeros."""
+    V, W0, H0 = make_problem(case)
+    if case['precision'] == 'f16':
+        V = V.half().float()
+    return V, W0, H0
+
+
+def host_images(F, precision: str):
+    """(hi, lo or None) image values of a factor, rounded on the host (the CPU tests; the GPU tests read them back)."""
+    return factor_image(np.asarray(F, dtype=np.float64), precision)

@@ -439,3 +439,289 @@ def test_seeded_fault_owner_fragments_of_the_neighbouring_wave():
     bad = dict(ok, den=ok['den'].copy())
     bad['den'][32:64] = ok['den'][0:32]
     _xb_verdict(s, ok, bad, '(h) owner fragments of wave 0 in wave 1', False)
+
+
+# ---- the dense loss pass: float64 model per partial, its bound, seeded faults ------------------------------------------
+def _loss_case(prefix):
+    return next(c for c in E.loss_cases(256) if c['id'].startswith(prefix))
+
+
+_LOSS_MEMO = {}
+
+
+def _loss_model(case, **kw):
+    """(plan, partials) of a loss case from its initial factors, images rounded on the host (memoised: the cap test and the
+    seeded-fault tests share the unfaulted models)."""
+    key = (case['id'], tuple(sorted((k, str(v)) for k, v in kw.items())))
+    if key not in _LOSS_MEMO:
+        prec, beta = case['precision'], case['beta']
+        plan = E.loss_plan(case['N'], case['C'], case['R'], prec, beta, 256, case['nsplit'], case['block_rows'], case['gram'])
+        V, W0, H0 = E.loss_problem(case)
+        lp = E.loss_partials(V.numpy(), E.host_images(H0.numpy(), prec), E.host_images(W0.numpy(), prec), beta, prec, plan, **kw)
+        _LOSS_MEMO[key] = (plan, lp)
+    return _LOSS_MEMO[key]
+
+
+@pytest.mark.parametrize('block_rows', [None, 128])
+@pytest.mark.parametrize('beta', [-1.0, 0.0, 0.3, 0.5, 1.0, 1.5, 2.0, 3.0])
+def test_unrounded_loss_partials_sum_to_the_oracle(beta, block_rows):
+    """rounding=False: the partials are a partition of beta_div(H W^T, V) -- every valid element once, no padded one -- on a
+    ragged shape (rows, columns and rank off every tile) with 30 % exact zeros in the target, for every beta branch, on the
+    ping-pong kernel's 256-row blocks (beta == 1) and on 128-row blocks."""
+    N, C, R = 150, 330, 7
+    g = torch.Generator().manual_seed(11)
+    V = torch.rand(N, C, generator=g, dtype=torch.float64)
+    V = torch.where(torch.rand(N, C, generator=g) < 0.3, torch.zeros((), dtype=torch.float64), V)
+    W = torch.rand(C, R, generator=g, dtype=torch.float64) + 0.05
+    H = torch.rand(N, R, generator=g, dtype=torch.float64) + 0.05
+    plan = E.loss_plan(N, C, R, 'f16', beta, 256, 2, block_rows)
+    assert plan['family'] == ('pp' if beta == 1.0 and block_rows is None else 'fused') and plan['nsplit'] == 2
+    lp = E.loss_partials(V.numpy(), (H.numpy(), None), (W.numpy(), None), beta, 'f16', plan, rounding=False)
+    want = float(O.beta_div(O.nmf_reconstruct(H, W), V, float(np.float32(beta))))     # (the library takes beta as a float: 0.3f)
+    assert lp['ref'].shape == (plan['nparts'],)
+    assert float(lp['ref'].sum()) == pytest.approx(want, rel=1e-10)
+
+
+def test_loss_plan_walks_the_loss_modes_tile_list():
+    """The loss runs on step_h's nsplit with ITS OWN tiles per split: rounded to even on the ping-pong kernel, not rounded on the
+    four-wave kernel -- whatever the MU family rounds to."""
+    sp = E.loss_plan(300, 1200, 256, 'f16', 1.0, 256, 4)
+    assert (sp['mu_family'], sp['family'], sp['mu_tiles'], sp['tiles']) == ('sp', 'fused', [8, 8, 4, 0], [5, 5, 5, 5])
+    sp2 = E.loss_plan(300, 1200, 100, 'f16', 0.5, 256, 4)
+    assert (sp2['mu_family'], sp2['family'], sp2['mu_tiles'], sp2['tiles']) == ('sp2', 'fused', [8, 8, 4, 0], [5, 5, 5, 5])
+    one = E.loss_plan(300, 200, 200, 'f16', 1.0, 256)
+    assert (one['mu_family'], one['family'], one['mu_tiles'], one['tiles']) == ('sp', 'fused', [4], [4])
+    xb = E.loss_plan(384, 700, 64, 'f16', 2.0, 256, 3, gram=True)
+    assert (xb['mu_family'], xb['family'], xb['mu_tiles'], xb['tiles']) == ('xb', 'fused', [4, 4, 4], [4, 4, 4])
+    pp = E.loss_plan(257, 1100, 33, 'f16', 1.0, 256, 4)
+    assert (pp['family'], pp['block_rows'], pp['tiles'], pp['nparts'], pp['tree']) == ('pp', 256, [6, 6, 6, 2], 8, 9)
+    assert E.loss_plan(257, 1700, 33, 'f16', 1.0, 256, 6)['tiles'] == [6, 6, 6, 6, 4, 0]
+    four = E.loss_plan(100, 2304, 24, 'bf16', 0.5, 256, 7)
+    assert (four['family'], four['tiles'], four['nparts'], four['tree']) == ('fused', [6] * 6 + [0], 14, 8)
+    assert E.s_chain(32, 'f16') == 19 and E.s_chain(128, 'bf16x3') == 41 and E.s_chain(256, 'f16') == 33
+    ids = [c['id'] for c in E.loss_cases(256)]
+    assert len(ids) == len(set(ids))
+
+
+def test_every_loss_case_bound_is_at_most_1e5_of_its_terms():
+    """Non-vacuity of the bound: for every case of the GPU matrix and every partial that owns a valid element, the derived bound
+    is at most LOSS_CAP = 1e-5 of the partial's sum |terms| (images rounded on the host).  A cap, not a measurement: a case
+    that exceeds it gets a shorter contraction (mu_emulation.LOSS_SHAPES), the cap stays."""
+    assert E.LOSS_CAP == 1e-5
+    for c in E.loss_cases(256):
+        plan, lp = _loss_model(c)
+        live = lp['abs_terms'] > 0
+        assert live.any(), c['id']
+        frac = lp['bound'][live] / lp['abs_terms'][live]
+        assert frac.max() <= E.LOSS_CAP, (c['id'], float(frac.max()))
+        assert (lp['bound'][~live] == 0).all() and (lp['ref'][~live] == 0).all(), c['id']
+        assert lp['n_chain'].max() == 32 * max(plan['tiles'])
+
+
+def _fp32_loss_partials(case):
+    """The loss pass executed in numpy fp32 in the kernel's order: loss_elem as written (np.log2 / np.exp2 on float32 are
+    within an ulp), one accumulator per lane over (tile, tt, d, half), six butterfly levels, the waves' tree.  S is the
+    float64 reconstruction rounded to fp32 once."""
+    prec, beta = case['precision'], case['beta']
+    plan = E.loss_plan(case['N'], case['C'], case['R'], prec, beta, 256, case['nsplit'], case['block_rows'], case['gram'])
+    V, W0, H0 = E.loss_problem(case)
+    f = np.float32
+    kind = E.beta_kind(beta)
+    S = E._recon(E.host_images(H0.numpy(), prec), E.host_images(W0.numpy(), prec), plan['m_pad'], plan['k_pad'],
+                 0.0 if kind == 'euc' else E.EPS).astype(f)
+    x = E._padded(E.stored_target(V.numpy(), prec), plan['m_pad'], plan['k_pad']).astype(f)
+    eps, ln2, b = f(E.EPS), f(0.6931471805599453), f(beta)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        if kind == 'euc':
+            d = S - x
+            l = f(0.5) * d * d
+        elif kind == 'kl':
+            l = x * ((np.log2(x + eps) - np.log2(S)) * ln2) - x + (S - eps)
+        elif kind == 'is':
+            xe = x + eps
+            l = xe * (f(1.0) / S) - (np.log2(xe) - np.log2(S)) * ln2 - f(1.0)
+        else:
+            xb = x + eps if beta < 0 else x
+            t1 = np.where(xb > 0, np.exp2(b * np.log2(np.where(xb > 0, xb, f(1.0)))), f(0.0)).astype(f)
+            sb1 = np.exp2((b - f(1.0)) * np.log2(S)).astype(f)
+            l = (t1 + (b - f(1.0)) * (sb1 * S) - b * xb * sb1) / (b * (b - f(1.0)))
+    assert l.dtype == np.float32
+    ok = (np.arange(plan['m_pad'])[:, None] < plan['M']) & (np.arange(plan['k_pad'])[None, :] < plan['K'])
+    l = np.where(ok, l, f(0.0))
+    br, ns, tps = plan['block_rows'], plan['nsplit'], plan['tps']
+    out = np.zeros(plan['nparts'], dtype=f)
+    for mb in range(plan['m_pad'] // br):
+        for ks in range(ns):
+            nt = plan['tiles'][ks]
+            if nt == 0:
+                continue
+            blk = l[mb * br:(mb + 1) * br, ks * tps * 64:(ks * tps + nt) * 64].reshape(br // 32, 32, nt, 2, 32)   # wave, j, tile, hl, slot
+            acc = np.zeros((br // 32, 32, 2), dtype=f)
+            for t in range(nt):
+                for sl in range(32):
+                    acc = acc + blk[:, :, t, :, sl]
+            lanes = acc.transpose(0, 2, 1).reshape(br // 32, 64)          # lane = 32 hl + j
+            for o in (32, 16, 8, 4, 2, 1):
+                lanes = lanes + lanes[:, np.arange(64) ^ o]
+            red = lanes[:, 0]
+            while len(red) > 1:
+                red = red[0::2] + red[1::2]
+            out[mb * ns + ks] = red[0]
+    return plan, out
+
+
+@pytest.mark.parametrize('prefix', ['pp-f16-b1-257x1100', 'fused-bf16x3-b0.5-200x330', 'fused-f16-b2-300x500', 'fused-bf16-b0-384x1100',
+                                    'fused-f16-b3-', 'fused-bf16-b-1-200x330', 'pp-f16r-b1-257x1100r33-ns4-fitted'])
+def test_fp32_execution_of_the_loss_stays_inside_the_bound(prefix):
+    """The bound holds for an fp32 execution in the kernel's order (so it is not too tight to be met), and that execution is
+    not the float64 value (so the comparison is not trivially zero)."""
+    c = _loss_case(prefix)
+    plan, got = _fp32_loss_partials(c)
+    _, lp = _loss_model(c)
+    ex = E.partial_excess(got, lp['ref'], lp['bound'])
+    assert ex.max() <= 1.0, (c['id'], float(ex.max()))
+    assert ex.max() > 0.0
+
+
+@pytest.mark.parametrize('beta', [0.5, 3.0, -1.0])
+def test_seeded_fault_loss_column_mask_dropped(beta):
+    """(a) ``k0 < a.K`` dropped on C % 64 != 0: every padded column of a valid row adds loss_elem(s = eps, x = 0).  At beta = 0.5
+    that is eps^0.5 / 0.5 = 6.9e-4 per element and the checker flags it by more than 10x where the padding is a sizeable share of
+    the tiles (200 x 330: 182 padded columns per row in split 1; the six of 520 x 250 move a partial by 0.19 of its bound).  At beta = 3 it is eps^3 / 3 =
+    5.6e-22 per element, below 1e-15 of a partial; at beta = -1 the padded element becomes x = eps against s = eps, a
+    divergence of EXACTLY zero (all three terms are powers of two).  At those two betas a kernel without the mask returns the
+    same fp32 words as one with it: no check of the output can tell them apart, and the sum is right either way.  The test pins
+    both halves: caught where the fault changes the value, provably harmless where it does not."""
+    c = _loss_case({0.5: 'fused-bf16x3-b0.5-200x330r24', 3.0: 'fused-bf16-b3-200x250r24', -1.0: 'fused-bf16-b-1-200x330r24'}[beta])
+    plan, ok = _loss_model(c)
+    _, bad = _loss_model(c, col_mask=False)
+    shift = np.abs(bad['ref'] - ok['ref'])
+    pad_cols = plan['k_pad'] - plan['K']
+    assert pad_cols > 0
+    if beta == 0.5:
+        ex = E.partial_excess(bad['ref'], ok['ref'], ok['bound'])
+        assert plan['tiles'] == [4, 4] and (shift[0::2] == 0).all()             # split 0 holds no padded column, split 1 holds 182
+        assert (ex[1::2] >= 10.0).all(), ex
+        assert shift.sum() == pytest.approx(plan['M'] * pad_cols * np.sqrt(E.EPS) / 0.5, rel=1e-9)
+    elif beta == 3.0:
+        assert shift.sum() == pytest.approx(plan['M'] * pad_cols * E.EPS ** 3 / 3.0, rel=1e-6)
+        live = ok['abs_terms'] > 0
+        assert (shift[live] <= 2.0 ** -40 * np.abs(ok['ref'][live])).all()          # far below half an ulp of the fp32 partial
+    else:
+        assert (shift == 0).all()
+
+
+def test_seeded_fault_loss_last_valid_row_dropped():
+    """(b) ``m0 < a.M`` off by one: row M - 1 is missing from the last row block's partials."""
+    for prefix in ('pp-f16-b1-257x1100r33-ns4', 'fused-bf16x3-b0.5-200x330'):
+        c = _loss_case(prefix)
+        plan, ok = _loss_model(c)
+        _, bad = _loss_model(c, m_valid=plan['M'] - 1)
+        ex = E.partial_excess(bad['ref'], ok['ref'], ok['bound'])
+        mb = (plan['M'] - 1) // plan['block_rows']
+        own = [mb * plan['nsplit'] + ks for ks in range(plan['nsplit']) if ok['abs_terms'][mb * plan['nsplit'] + ks] > 0]
+        assert own and (ex[own] >= 10.0).all(), (prefix, ex)
+
+
+def test_seeded_faults_loss_partials_swapped_or_a_tile_skipped_pass_the_total():
+    """(c) two partials swapped and (d) the last tile of one split skipped: the per-partial check flags both by more than 10x,
+    the total at rel = 2e-4 -- what test_gpu_parity.py holds the loss to -- sees neither.  257 x 1100 on 256-row blocks,
+    tiles [6, 6, 6, 2]: the second row block holds one row, the last tile of split 2 twelve valid columns."""
+    c = _loss_case('pp-f16-b1-257x1100r33-ns4')
+    plan, ok = _loss_model(c)
+    assert plan['tiles'] == [6, 6, 6, 2]
+    total = ok['ref'].sum()
+    # (c)
+    got = ok['ref'].copy()
+    got[[0, 1]] = got[[1, 0]]
+    ex = E.partial_excess(got, ok['ref'], ok['bound'])
+    assert ex[0] >= 10.0 and ex[1] >= 10.0
+    assert got.sum() == pytest.approx(total, rel=2e-4)
+    # (d): workgroup (row block 1, split 2) walks five of its six tiles
+    _, bad = _loss_model(c, tiles=[6, 6, 5, 2])
+    ex = E.partial_excess(bad['ref'], ok['ref'], ok['bound'])
+    assert ex[4 + 2] >= 10.0 and ex[2] >= 10.0
+    got = ok['ref'].copy()
+    got[4 + 2] = bad['ref'][4 + 2]                      # the fault in ONE workgroup
+    assert E.partial_excess(got, ok['ref'], ok['bound'])[4 + 2] >= 10.0
+    assert got.sum() == pytest.approx(total, rel=2e-4)
+
+
+def test_seeded_fault_loss_empty_split_keeps_its_poison():
+    """(e) an empty split (or one of padding only) that does not write its slot: the slot must hold exactly 0.0."""
+    for prefix, empty in (('pp-f16-b1-257x1700r33-ns6', 5), ('fused-bf16-b0.5-100x2304r24-ns7', 6)):
+        c = _loss_case(prefix)
+        plan, ok = _loss_model(c)
+        assert plan['tiles'][empty] == 0 and ok['bound'][empty] == 0
+        for poison in (float('nan'), 1e-30, -0.0 + 1e-45):
+            got = ok['ref'].copy()
+            got[empty] = poison
+            assert E.partial_excess(got, ok['ref'], ok['bound'])[empty] >= 10.0
+        assert E.partial_excess(ok['ref'], ok['ref'], ok['bound']).max() == 0.0
+    # a split of padding only ([6, 6, 6, 2]: tiles 18, 19 lie beyond column 1100) and a row block of padding only
+    plan, ok = _loss_model(_loss_case('pp-f16-b1-257x1100r33-ns4'))
+    assert ok['bound'][3] == 0 and ok['bound'][7] == 0 and ok['n_chain'][3] == 64
+    plan, ok = _loss_model(_loss_case('fused-bf16-b0.5-100x2304r24-ns7'))
+    assert (ok['bound'][7:] == 0).all() and (ok['bound'][:6] > 0).all()
+
+
+def test_seeded_fault_loss_eps_dropped_from_the_log():
+    """(f) log(x) for log(x + eps): 0 * log2(0) is NaN in every partial that owns a zero of the target."""
+    c = _loss_case('pp-f16-b1-300x1000r64-ns2-zeros')
+    plan, ok = _loss_model(c)
+    _, bad = _loss_model(c, eps_in_log=False)
+    ex = E.partial_excess(bad['ref'], ok['ref'], ok['bound'])
+    live = ok['abs_terms'] > 0
+    assert live.sum() == 4 and (ex[live] >= 10.0).all()
+    # ... and on a target without zeros the dropped eps is still seen: x ln(x + eps) - x ln x ~ eps per element
+    c = _loss_case('pp-f16-b1-257x1100r33-ns4')
+    _, ok = _loss_model(c)
+    _, bad = _loss_model(c, eps_in_log=False)
+    assert np.isfinite(bad['ref']).all()
+
+
+def _riding_model(case, **kw):
+    prec = case['precision']
+    plan = E.riding_plan(case['N'], case['C'], case['R'], prec, 256, case['nsplit'])
+    V, W0, H0 = E.riding_problem(case)
+    return plan, V, E.riding_total(V.numpy(), E.host_images(W0.numpy(), prec), E.host_images(H0.numpy(), prec), prec, plan, **kw)
+
+
+@pytest.mark.parametrize('case', E.RIDING_CASES, ids=lambda c: c['id'])
+def test_riding_model_is_the_kl_divergence(case):
+    """The value assembled from the pairs the way riding_finish_kernel does is the float64 KL divergence of the fp32 target
+    within the bound (the stored target's rounding is the only difference in exact arithmetic), and the bound is small
+    against the terms."""
+    plan, V, rt = _riding_model(case)
+    assert abs(rt['kernel_value'] - rt['ref']) <= rt['bound']
+    H0, W0 = E.riding_problem(case)[2], E.riding_problem(case)[1]
+    want = float(O.beta_div(O.nmf_reconstruct(torch.from_numpy(E.host_images(H0.numpy(), case['precision'])[0]),
+                                              torch.from_numpy(E.host_images(W0.numpy(), case['precision'])[0])), V.double(), 1.0))
+    assert rt['ref'] == pytest.approx(want, rel=1e-10)
+    S = E._recon((E.host_images(W0.numpy(), case['precision'])[0], None), (E.host_images(H0.numpy(), case['precision'])[0], None),
+                 plan['m_pad'], plan['k_pad'], E.EPS)[:plan['M'], :plan['K']]
+    x = V.double().numpy().T
+    terms = (np.abs(x * np.log(x + E.EPS)) + np.abs(x * np.log(S)) + np.abs(x) + np.abs(S)).sum()
+    assert rt['bound'] <= 2 * E.LOSS_CAP * terms, (rt['bound'] / terms)
+
+
+def test_seeded_fault_riding_n_all_counts_valid_elements_only():
+    """(g) the device subtracts n_all * eps for EVERY processed element (each padded one contributed exactly eps to sum s); with
+    the valid count instead the loss is too large by (n_all - M K) eps.  1 x 300 rank 1: 131 072 processed, 300 valid."""
+    case = next(c for c in E.RIDING_CASES if c['id'].startswith('f16-1x300'))
+    plan, V, ok = _riding_model(case)
+    assert plan['n_all'] == 512 * 256 and plan['tiles'] == [4]
+    _, _, bad = _riding_model(case, n_all=300)
+    assert abs(ok['kernel_value'] - ok['ref']) <= ok['bound']
+    assert abs(bad['kernel_value'] - ok['ref']) >= 10.0 * ok['bound']
+    assert bad['kernel_value'] - ok['kernel_value'] == pytest.approx((plan['n_all'] - 300) * E.EPS, rel=1e-6)
+
+
+def test_beta_div_bound_is_the_oracle_value():
+    g = torch.Generator().manual_seed(5)
+    x, y = torch.rand(700, generator=g), torch.rand(700, generator=g)
+    y = torch.where(torch.rand(700, generator=g) < 0.3, torch.zeros(()), y)
+    for beta in (-1.0, 0.0, 0.5, 1.0, 1.5, 2.0, 3.0):
+        ref, bound = E.beta_div_bound(x.numpy(), y.numpy(), beta)
+        assert ref == pytest.approx(float(O.beta_div(x.double(), y.double(), beta)), rel=1e-9)
+        assert 0 < bound <= 1e-5 * float(E.loss_abs_terms(x.double().numpy() + (0 if beta == 2 else E.EPS), y.double().numpy(), beta).sum())
