@@ -69,6 +69,9 @@ extern "C" {
                                   iteration of a row in one launch; added at ABI 10, additive);
                                   nmfmu_hals_sweep (NMF.fit(solver='hals'): the coordinate-descent sweep over the rank for
                                   beta == 2; added at ABI 10, additive);
+                                  nmfmu_sp_ccd_sweep / nmfmu_sp_ccd_limit / nmfmu_sp_ccd_wg_waves / nmfmu_sp_ccd_lds_rows (NMF.fit(solver='ccd'):
+                                  coordinate descent over the stored entries of a missing-data target, beta == 2; added at
+                                  ABI 10, additive);
                                10: nmfmu_plca_normalize / nmfmu_plca_z / nmfmu_plca3 take alpha as double (an argument changed its
                                   type: not additive).  The Dirichlet prior adds fp32(alpha - 1) with the subtraction in double,
                                   as the reference's in-place add does; fp32(alpha) - 1.f was off by 4.7e-5 relative at
@@ -900,6 +903,39 @@ int nmfmu_fold_in(const int32_t* rowptr, const int32_t* colidx, const float* val
  * device work. */
 int nmfmu_hals_sweep(float* f, int rows, int rank, const float* a, int64_t lda, const float* gram, float l1, float l2,
                      void* stream);
+
+/* ---- CCD: coordinate descent over the STORED entries, beta == 2 (additive entries; ccd.py) -------------
+ * nmfmu_sp_ccd_sweep: one pass over the rank on owner [n_rows][rank], in place, for a target whose unstored entries are
+ * MISSING.  rowptr / idx / vals: the owner side's CSR (H) or CSC (W) arrays; idx holds rows of panel [n_panel][rank].  Every
+ * owner row i with stored entries e (panel row j_e, value v_e), on its own:
+ *   r_e = v_e - sum_k owner[i][k] panel[j_e][k]                       (k ascending, one fused multiply-add chain from 0)
+ *   for k = 0 .. rank-1:  d = sum_e panel[j_e][k]^2,  n = sum_e r_e panel[j_e][k]
+ *                         f' = max(eps, (fma(owner[i][k], d, n) - l1) / ((d + l2) + eps)),   eps = 2^-23
+ *                         r_e = fma(-(f' - owner[i][k]), panel[j_e][k], r_e) for every e;   owner[i][k] = f'
+ * -- the exact minimiser of 1/2 sum_e (v_e - <owner[i], panel[j_e]>)^2 + l1 sum f + l2/2 |f|^2 along the coordinate, floored
+ * at eps.  A row without entries is not touched.
+ * Arithmetic: fp32.  A row of at most wg_rows entries (0: nmfmu_sp_ccd_limit()) is worked by one wave, a longer one by a
+ * workgroup of NW = nmfmu_sp_ccd_wg_waves() waves (two launches over the same list; which one takes a row is a function of
+ * its count and wg_rows).  Rows are taken in the order of `order` (int32 [n_rows], NULL: 0 .. n_rows-1; longest first keeps
+ * the launches short, no result depends on it).  With NW waves on a row (1 or 16), entry e belongs to lane e mod 64 of wave
+ * (e / 64) mod NW; d and n are per-lane fused multiply-add chains over the lane's entries in ascending e, then an xor
+ * butterfly 32 .. 1 per wave, then the waves' totals added in wave order.
+ * limit: a row of at most limit NW entries keeps its residuals in registers (0: nmfmu_sp_ccd_limit() = 512, also the largest
+ * value); a longer row keeps them in its slice scratch[rowptr[i] .. rowptr[i + 1]) of scratch [nnz floats], which no other
+ * row touches.  lds_rows: a one-wave row of at most min(lds_rows, nmfmu_sp_ccd_lds_rows(rank)) entries copies its panel rows
+ * to LDS once; the other rows gather panel[j_e][k] from panel_t [rank][n_panel], a transposed copy this entry writes first
+ * (one more small launch), or from panel itself when panel_t is NULL.  The same operations in the same order wherever the
+ * residuals and the panel values live: a row's bits depend on that row of owner, its entries, panel, l1, l2 and wg_rows
+ * alone -- not on limit, lds_rows, panel_t, order or the other rows.  Plain vector stores, no atomics: a repeated call is
+ * bitwise identical.  panel, idx, vals are only read.
+ * Null rowptr / idx / vals / owner / panel / scratch, owner == panel, n_rows < 0, n_panel <= 0, rank <= 0, limit outside
+ * 0 .. 512, lds_rows < 0, wg_rows < 0: NMFMU_ERR_ARG; rank > 256: NMFMU_ERR_UNSUPPORTED -- both before any device work. */
+int nmfmu_sp_ccd_limit(void);          /* 512: entries per row whose residuals stay in registers */
+int nmfmu_sp_ccd_wg_waves(void);       /* 16: waves of the workgroup that takes a row of more than wg_rows entries */
+int nmfmu_sp_ccd_lds_rows(int rank);   /* entries per row whose panel rows fit the LDS stage; 0 outside rank 1 .. 256 */
+int nmfmu_sp_ccd_sweep(const int32_t* rowptr, const int32_t* idx, const float* vals, const int32_t* order, int n_rows,
+                       float* owner, const float* panel, int n_panel, int rank, float l1, float l2, float* scratch,
+                       float* panel_t, int limit, int lds_rows, int wg_rows, void* stream);
 
 /* ---- shift-invariant PLCA (SIPLCA / SIPLCA2 / SIPLCA3, plca.py:376-606) on the NMFD GEMM path ----------------------
  * Same EM update as PLCA with W (C, R, *T), H (B, R, *Lh): factors are addressed [outer][rank][inner], the unscaled

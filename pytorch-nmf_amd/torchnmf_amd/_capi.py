@@ -185,6 +185,12 @@ SIGNATURES = {
                                 C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     'nmfmu_hals_sweep': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_float,
                                    C.c_void_p]),
+    'nmfmu_sp_ccd_limit': (C.c_int, []),
+    'nmfmu_sp_ccd_wg_waves': (C.c_int, []),
+    'nmfmu_sp_ccd_lds_rows': (C.c_int, [C.c_int]),
+    'nmfmu_sp_ccd_sweep': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                     C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                     C.c_void_p]),
     'nmfmu_pack_factor_scaled': (C.c_int, [C.POINTER(Factor), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'nmfmu_plca_part_bytes': (C.c_size_t, [C.c_int, C.c_int]),
     'nmfmu_plca_em': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,

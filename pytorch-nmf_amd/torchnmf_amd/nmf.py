@@ -427,9 +427,30 @@ class BaseComponent(nn.Module):
                          fit can continue from the result.  Loss, stop rule and return value as above; alpha / l1_ratio
                          penalise as in the MU denominators.  Dense and sparse-COO (unstored='zero') targets, NMF only,
                          rank <= 256, not sharded.  Exact fp32: ``precision`` is ignored and ``last_precision`` is 'fp32'.
+                         'ccd': the same coordinate minimiser for a MISSING-DATA fit (beta == 2, unstored='missing'), where
+                         the quadratic of a row is built from its stored entries only and one Gram matrix cannot serve:
+                         cyclic coordinate descent with a maintained residual over the stored entries (Yu, Hsieh, Si,
+                         Dhillon 2012; ``ccd.ccd_sweep``), O(nnz * rank) per half-step like the masked multiplicative
+                         update.  The factors are first scaled by the scalar that minimises the loss over the stored
+                         entries and floored at eps (``ccd.CcdEngine``); a row or column without a stored entry is left as
+                         it is.  Loss (``beta_div`` over the stored entries), stop rule, return value and alpha / l1_ratio
+                         as for 'hals'.  Sparse-COO targets, NMF only, rank <= 256, not sharded, exact fp32.
         """
-        if solver not in ('mu', 'hals'):
-            raise ValueError(f"solver must be 'mu' or 'hals', got {solver!r}")
+        if solver not in ('mu', 'hals', 'ccd'):
+            raise ValueError(f"solver must be 'mu', 'hals' or 'ccd', got {solver!r}")
+        if solver == 'ccd':
+            if float(beta) != 2.0:
+                raise NotImplementedError(f"solver='ccd': the coordinate minimiser is closed-form only for beta = 2, got "
+                                          f"beta = {beta:g}")
+            if not isinstance(self, NMF):
+                raise NotImplementedError(f"solver='ccd' is implemented for NMF only, not {type(self).__name__}")
+            if unstored != 'missing':
+                raise NotImplementedError("solver='ccd' fits the stored entries only and needs unstored='missing'; for a "
+                                          "target whose unstored entries are observed zeros use solver='hals'")
+            if process_group is not None:
+                raise NotImplementedError("solver='ccd' is not sharded (process_group must be None)")
+            if self.W is not None and self.W.shape[1] > 256:
+                raise NotImplementedError(f"solver='ccd': rank {self.W.shape[1]} > 256, the limit of the sparse kernels")
         if solver == 'hals':
             if float(beta) != 2.0:
                 raise NotImplementedError(f"solver='hals': the coordinate minimiser is closed-form only for beta = 2, got "
@@ -438,7 +459,7 @@ class BaseComponent(nn.Module):
                 raise NotImplementedError(f"solver='hals' is implemented for NMF only, not {type(self).__name__}")
             if unstored == 'missing':
                 raise NotImplementedError("solver='hals': the Gram shortcut needs unstored = 'zero' (with unstored='missing' "
-                                          "the denominator runs over the stored entries only)")
+                                          "the denominator runs over the stored entries only: use solver='ccd')")
             if process_group is not None:
                 raise NotImplementedError("solver='hals' is not sharded (process_group must be None)")
             if self.W is not None and self.W.shape[1] > 256:
@@ -483,7 +504,12 @@ class BaseComponent(nn.Module):
         V = V.detach()
         if V.dtype != torch.float32:
             V = V.float()
-        if solver == 'hals':
+        if solver == 'ccd':
+            from .ccd import CcdEngine
+            if not (W.data.is_contiguous() and H.data.is_contiguous()):
+                W.data, H.data = W.data.contiguous(), H.data.contiguous()
+            eng = CcdEngine(V, W.data, H.data, l1, l2, update_W=W.requires_grad, update_H=H.requires_grad)
+        elif solver == 'hals':
             from .hals import HalsEngine
             if not (W.data.is_contiguous() and H.data.is_contiguous()):
                 W.data, H.data = W.data.contiguous(), H.data.contiguous()
