@@ -123,6 +123,12 @@ extern "C" {
                                    nmfmu_mu_apply / nmfmu_trainer_apply alike; the buffers must still be allocated).  nmfmu_loss
                                    treats it as NMFMU_STAGE_DMA; any other step answers NMFMU_ERR_UNSUPPORTED.  Appended under
                                    ABI 9: no struct layout changes */
+#define NMFMU_STAGE_DMA_SP128 5 /* as NMFMU_STAGE_DMA_LDSTR (same promise about p2_*, same steps refused), and the MU half-step with
+                                   fp16 operands and a 2-byte target (NMFMU_PREC_F16) at padded rank 128 runs the
+                                   software-pipelined four-wave kernel with 64 owner rows per wave (nmfmu_sp128.h; tiles per
+                                   workgroup rounded up to a multiple of four): same MFMA order per accumulator, bit-identical
+                                   results at equal contraction splits.  The loss-carrying half-step stays on the ping-pong kernel;
+                                   any other precision answers NMFMU_ERR_UNSUPPORTED.  Appended under ABI 10: no struct layout changes */
 #define NMFMU_STAGE_DMA_SPLIT 2 /* as NMFMU_STAGE_DMA, and panel.p1_* / panel.p2_* are images of DIFFERENT matrices (PLCA: the
                                    Z-scaled factor for the reconstruction, the unscaled one for the second GEMM).  Since ABI 6
                                    the single-plane four-wave kernels stage ONE panel image and gather the second GEMM's

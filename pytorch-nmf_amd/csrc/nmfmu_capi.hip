@@ -13,6 +13,7 @@
 #include "nmfmu_pp.h"
 #include "nmfmu_sp.h"
 #include "nmfmu_sp2.h"
+#include "nmfmu_sp128.h"
 
 #ifndef NMFMU_SP
 #define NMFMU_SP 1   // (A/B switch of round 6; 0 = padded rank 256, beta == 1, fp16 stays on the four-wave kernel)
@@ -57,6 +58,10 @@ static bool pp_eligible(int r_pad, int precision, float beta) {
 static bool pp_ldstr_eligible(int r_pad, int precision, float beta) {
   return pp_eligible(r_pad, precision, beta) && pp_trl_available(r_pad, is_f16(precision) ? kOpF16 : kOpBf16, kModeMU);
 }
+// ... and the MU half-steps NMFMU_STAGE_DMA_SP128 moves to the software-pipelined kernel with 64 owner rows per wave (nmfmu_sp128.h)
+static bool sp128_eligible(int r_pad, int precision, float beta) {
+  return pp_ldstr_eligible(r_pad, precision, beta) && precision == NMFMU_PREC_F16 && sp128_available(r_pad, kOpF16, kModeMU);
+}
 // which half-steps the software-pipelined one-wave-per-SIMD kernel serves (nmfmu_sp.h): beta == 1, fp16 operands and target,
 // padded rank 256 -- the kernel of configs[4]'s shard
 static bool sp_eligible(int r_pad, int precision, float beta) {
@@ -89,12 +94,14 @@ int fused_dispatch(const nmfmu_step* st, int mode, float* loss_part, int M, int 
   if (st->owner.rows_pad % kRowPad || st->panel.rows_pad % kRowPad) return NMFMU_ERR_ARG;
   if (st->block_rows != 128 && st->block_rows != 256) return NMFMU_ERR_ARG;
   if (st->stage != NMFMU_STAGE_DMA && st->stage != NMFMU_STAGE_DMA_SPLIT && st->stage != NMFMU_STAGE_DMA_NOP2 &&
-      st->stage != NMFMU_STAGE_DMA_LDSTR)
+      st->stage != NMFMU_STAGE_DMA_LDSTR && st->stage != NMFMU_STAGE_DMA_SP128)
     return NMFMU_ERR_UNSUPPORTED;   // (register staging: no longer built)
   // one panel image, the transposed tile built in LDS: the ping-pong kernel's MU half-step only (the loss reads p1 alone anyway)
-  const bool ldstr = st->stage == NMFMU_STAGE_DMA_LDSTR && mode != kModeLoss;
+  const bool sp128 = st->stage == NMFMU_STAGE_DMA_SP128;
+  const bool ldstr = (st->stage == NMFMU_STAGE_DMA_LDSTR || sp128) && mode != kModeLoss;
   if (ldstr && (mode != kModeMU || st->block_rows != 256 || !pp_ldstr_eligible(st->r_pad, st->precision, st->beta)))
     return NMFMU_ERR_UNSUPPORTED;
+  if (sp128 && !sp128_eligible(st->r_pad, st->precision, st->beta)) return NMFMU_ERR_UNSUPPORTED;
   // split panel (PLCA: p1 = the Z-scaled factor, p2 = the unscaled one): the instantiation that stages BOTH images
   if (st->stage == NMFMU_STAGE_DMA_SPLIT && mode == kModeMU && !(st->precision == NMFMU_PREC_BF16X3)) {
     if (nmfmu_beta_kind(st->beta) != NMFMU_BETA_KL || st->block_rows != 128) return NMFMU_ERR_UNSUPPORTED;
@@ -165,6 +172,10 @@ int fused_dispatch(const nmfmu_step* st, int mode, float* loss_part, int M, int 
     if (mode == kModeMU && g_pp_debug) a.debug = g_pp_debug;
 #endif
     if (ldstr) a.o2_hi = nullptr;   // nobody reads the owner's transposed image: the fused apply skips it
+    if (sp128 && mode == kModeMU && !loss_part) {   // (the loss-carrying half-step stays on the ping-pong kernel)
+      a.tiles_per_split = (a.tiles_per_split + 3) & ~3;   // its tile loop runs in groups of four (ring slot = tile & 3)
+      return launch_sp128(st->r_pad, kOpF16, a, grid, s);
+    }
     return launch_pp(st->r_pad, is_f16(st->precision) ? kOpF16 : kOpBf16, mode, a, grid, s, st->precision == NMFMU_PREC_F16R,
                      /*riding loss*/ mode == kModeMU && loss_part != nullptr, ldstr);
   }
@@ -408,7 +419,7 @@ static int apply_common(const nmfmu_step* st, const float* num, const float* den
   a.status = st->status;
   if (!a.p1_hi || !a.p2_hi || !a.colsum || !a.colsum_part) return NMFMU_ERR_ARG;
   if (st->stage == NMFMU_STAGE_DMA_NOP2 && sp_eligible(st->r_pad, st->precision, st->beta)) a.p2_hi = a.p2_lo = nullptr;   // (see nmfmu.h)
-  if (st->stage == NMFMU_STAGE_DMA_LDSTR) {
+  if (st->stage == NMFMU_STAGE_DMA_LDSTR || st->stage == NMFMU_STAGE_DMA_SP128) {
     if (st->block_rows != 256 || !pp_ldstr_eligible(st->r_pad, st->precision, st->beta)) return NMFMU_ERR_UNSUPPORTED;
     a.p2_hi = a.p2_lo = nullptr;
   }

@@ -23,6 +23,8 @@ STAGE_REG, STAGE_DMA, STAGE_DMA_SPLIT = 0, 1, 2
 STAGE_DMA_NOP2 = 3          # as STAGE_DMA; nothing reads the factors' transposed images (include/nmfmu.h)
 STAGE_DMA_LDSTR = 4         # ping-pong MU half-step at padded rank 128: one panel image, the transposed tile built in LDS;
                             # nothing reads or refreshes the factors' transposed images (include/nmfmu.h)
+STAGE_DMA_SP128 = 5         # as STAGE_DMA_LDSTR; the 'f16' MU half-step at padded rank 128 on the software-pipelined four-wave
+                            # kernel with 64 owner rows per wave (csrc/nmfmu_sp128.h)
 BETA_KL, BETA_EUC, BETA_IS, BETA_GEN = 0, 1, 2, 3
 KERNEL_FUSED, KERNEL_PP, KERNEL_SP = 0, 1, 2
 

@@ -551,6 +551,7 @@ class DenseMU(AsyncLossMixin):
         self.precision = _capi.PRECISIONS[precision]
         if not self.be.supported(self.r_pad, self.precision):
             raise NotImplementedError(f'precision {precision!r} is not available for rank {R} (padded {self.r_pad})')
+        sp128_auto = False
         if stage is None:
             # (round 6) beta == 1 at padded rank 256 with fp16 operands runs the software-pipelined kernel in BOTH half-steps and
             # for the loss: ONE image per factor, GEMM2's operand gathered from it -- nothing reads the transposed images, so
@@ -567,6 +568,7 @@ class DenseMU(AsyncLossMixin):
                     and self.be.pp_lds_transpose_supported(self.r_pad, self.precision, float(beta))
                     and self.be.block_rows(self.r_pad, self.precision, float(beta)) == 256):
                 stage = _capi.STAGE_DMA_LDSTR
+                sp128_auto = self.precision == _capi.PREC_F16 and os.environ.get('TORCHNMF_AMD_SP128', '1') != '0'
         # beta == 2 without the reconstruction (nmf.py:61-63 has no eps inside its grad_outputs): numerator = one streaming
         # GEMM over X, denominator through the panel's rank x rank Gram matrix -- a third of the MFMA work, HBM-bound.
         # fit()'s engines only (allow_gram): BetaMu reads numerator AND denominator slabs (p.grad = pos - neg).
@@ -605,6 +607,20 @@ class DenseMU(AsyncLossMixin):
             ns_w = self._nsplit(c_pad, n_pad, brw, dev)
             self.step_w = StepBuf(xp_w, self.fW, self.fH, R, self.r_pad, ns_w, self.precision, stage, brw, self.beta,
                                   gamma, l1, l2, need_den=need_den, status=self.status)
+        # 'f16' on the one-image path, both half-steps with at least one workgroup per CU: the software-pipelined four-wave form
+        # with 64 owner rows per wave (NMFMU_STAGE_DMA_SP128; bit-identical to the ping-pong kernel at equal splits, whole
+        # groups of four tiles per workgroup).  Launches that fill the chip run at the socket's power limit, which is where
+        # it was measured to pay (-3.6 % per iteration at configs[1], profiles/r08_sp128_ab.md); smaller launches were not
+        # measured and stay on the ping-pong kernel; so do contractions that do not split into whole groups of four tiles (the
+        # two kernels would round the split differently: no longer the same sums).  TORCHNMF_AMD_SP128=0 keeps the ping-pong
+        # kernel everywhere (A/B).
+        if sp128_auto and dev.type == 'cuda':
+            ncu = torch.cuda.get_device_properties(dev).multi_processor_count
+            steps = (self.step_h, self.step_w)
+            if all(st.block_rows == 256 and (st.owner.rows_pad // 256) * st.nsplit >= ncu
+                   and (st.panel.rows_pad // 64) % (4 * st.nsplit) == 0 for st in steps):
+                for st in steps:
+                    st.struct.stage = _capi.STAGE_DMA_SP128
         self.gm = self.be.gram_alloc(self.r_pad, dev) if self.gram_path else None
         self.timer: Optional[KernelTimer] = None   # bench.py: times the fused launches live
         self.refresh_images()
