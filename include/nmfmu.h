@@ -129,6 +129,10 @@ extern "C" {
                                    workgroup rounded up to a multiple of four): same MFMA order per accumulator, bit-identical
                                    results at equal contraction splits.  The loss-carrying half-step stays on the ping-pong kernel;
                                    any other precision answers NMFMU_ERR_UNSUPPORTED.  Appended under ABI 10: no struct layout changes */
+#define NMFMU_STAGE_DMA_SP128_RB0 6 /* as NMFMU_STAGE_DMA_SP128 in every respect but the placement of the kernel's ratio stage: the
+                                       whole of a tile's ratio stage stays behind the first GEMM of the next tile (RB = 0 in
+                                       nmfmu_sp128.h), where NMFMU_STAGE_DMA_SP128 runs the shipped placement.  Bit-identical
+                                       results; kept as the other arm of an A/B in one library.  No struct layout changes */
 #define NMFMU_STAGE_DMA_SPLIT 2 /* as NMFMU_STAGE_DMA, and panel.p1_* / panel.p2_* are images of DIFFERENT matrices (PLCA: the
                                    Z-scaled factor for the reconstruction, the unscaled one for the second GEMM).  Since ABI 6
                                    the single-plane four-wave kernels stage ONE panel image and gather the second GEMM's

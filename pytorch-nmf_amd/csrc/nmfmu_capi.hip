@@ -94,10 +94,11 @@ int fused_dispatch(const nmfmu_step* st, int mode, float* loss_part, int M, int 
   if (st->owner.rows_pad % kRowPad || st->panel.rows_pad % kRowPad) return NMFMU_ERR_ARG;
   if (st->block_rows != 128 && st->block_rows != 256) return NMFMU_ERR_ARG;
   if (st->stage != NMFMU_STAGE_DMA && st->stage != NMFMU_STAGE_DMA_SPLIT && st->stage != NMFMU_STAGE_DMA_NOP2 &&
-      st->stage != NMFMU_STAGE_DMA_LDSTR && st->stage != NMFMU_STAGE_DMA_SP128)
+      st->stage != NMFMU_STAGE_DMA_LDSTR && st->stage != NMFMU_STAGE_DMA_SP128 && st->stage != NMFMU_STAGE_DMA_SP128_RB0)
     return NMFMU_ERR_UNSUPPORTED;   // (register staging: no longer built)
   // one panel image, the transposed tile built in LDS: the ping-pong kernel's MU half-step only (the loss reads p1 alone anyway)
-  const bool sp128 = st->stage == NMFMU_STAGE_DMA_SP128;
+  const bool sp128_rb0 = st->stage == NMFMU_STAGE_DMA_SP128_RB0;   // (the same kernel on its RB = 0 schedule: A/B arm)
+  const bool sp128 = st->stage == NMFMU_STAGE_DMA_SP128 || sp128_rb0;
   const bool ldstr = (st->stage == NMFMU_STAGE_DMA_LDSTR || sp128) && mode != kModeLoss;
   if (ldstr && (mode != kModeMU || st->block_rows != 256 || !pp_ldstr_eligible(st->r_pad, st->precision, st->beta)))
     return NMFMU_ERR_UNSUPPORTED;
@@ -174,7 +175,7 @@ int fused_dispatch(const nmfmu_step* st, int mode, float* loss_part, int M, int 
     if (ldstr) a.o2_hi = nullptr;   // nobody reads the owner's transposed image: the fused apply skips it
     if (sp128 && mode == kModeMU && !loss_part) {   // (the loss-carrying half-step stays on the ping-pong kernel)
       a.tiles_per_split = (a.tiles_per_split + 3) & ~3;   // its tile loop runs in groups of four (ring slot = tile & 3)
-      return launch_sp128(st->r_pad, kOpF16, a, grid, s);
+      return sp128_rb0 ? launch_sp128_rb0(st->r_pad, kOpF16, a, grid, s) : launch_sp128(st->r_pad, kOpF16, a, grid, s);
     }
     return launch_pp(st->r_pad, is_f16(st->precision) ? kOpF16 : kOpBf16, mode, a, grid, s, st->precision == NMFMU_PREC_F16R,
                      /*riding loss*/ mode == kModeMU && loss_part != nullptr, ldstr);
@@ -419,7 +420,7 @@ static int apply_common(const nmfmu_step* st, const float* num, const float* den
   a.status = st->status;
   if (!a.p1_hi || !a.p2_hi || !a.colsum || !a.colsum_part) return NMFMU_ERR_ARG;
   if (st->stage == NMFMU_STAGE_DMA_NOP2 && sp_eligible(st->r_pad, st->precision, st->beta)) a.p2_hi = a.p2_lo = nullptr;   // (see nmfmu.h)
-  if (st->stage == NMFMU_STAGE_DMA_LDSTR || st->stage == NMFMU_STAGE_DMA_SP128) {
+  if (st->stage == NMFMU_STAGE_DMA_LDSTR || st->stage == NMFMU_STAGE_DMA_SP128 || st->stage == NMFMU_STAGE_DMA_SP128_RB0) {
     if (st->block_rows != 256 || !pp_ldstr_eligible(st->r_pad, st->precision, st->beta)) return NMFMU_ERR_UNSUPPORTED;
     a.p2_hi = a.p2_lo = nullptr;
   }

@@ -15,6 +15,9 @@
 //                                                              t+3 (4 pieces per wave), the 8 X loads of tile t+2
 //               s_waitcnt vmcnt(12)                            (X(t+1) has landed)
 //
+// Where the ratio stage's VALU sits is a template parameter (RB, below): the shipped instance runs RB of tile t+1's 64
+// reciprocals per lane in the gaps of phase B(t) and spreads the rest of the stage over phase A(t+1) by issue cost.
+//
 // The panel ring has four 16 KiB slots = 64 KiB: every operand is base register + 16-bit immediate (as nmfmu_sp2.h).
 // Register plan: accumulators (2 x 4 x 16 = 128) and owner fragments (2 x 8 x 4 = 64) in AGPRs; two S tiles (2 x 64), the
 // ratios (32), the eps seed tile (16), X (2 x 32), the operand rings and 24 LDS address registers in VGPRs (hipcc lets
@@ -42,9 +45,86 @@ struct SP128Cfg {
   static_assert(N1 == 16 && N2 == 16 && NPW == 4 && NSLOT * IMG <= 65536, "schedule tables below; every LDS offset an immediate");
 };
 
-template <int OPT>
+// ---- placement of the ratio stage (template parameter RB of sp128_kernel; tests/test_sp128_respace.py replays these tables).
+// RB = 0 is the schedule above: all of tile t's ratio stage in phase A(t), five instructions per MFMA gap.  RB > 0 moves the
+// first RB reciprocals of tile t+1 into the MFMA gaps of phase B(t) -- S(t+1) is complete when phase A(t) ends and nothing
+// writes its buffer before GEMM1(t+3) -- and re-spaces what stays in phase A by issue cost (transcendental = 2 plain).  Every
+// instruction works in place on the S register: reciprocal, multiply by the fp16 half of the X word, then the pack reads two.
+//
+// Units of four elements are taken in the order their S tiles complete: unit u = (tt = u >> 3, og = (u >> 2) & 1, d-pair
+// u & 3); element x = 4 u + pos, pack y = 2 u + h.
+// hipcc pads (s_nop 0) in front of an asm statement that touches a register an earlier asm statement wrote unless one of its
+// OWN instructions -- scalar upkeep, or a pad it has already placed -- lies between the two: asm statements count as no wait
+// state.  The MFMA chains (S: every second entry, accumulators and operand ring: every fourth) owe such a pad about every
+// second entry; with hipcc's scalar code kept at the seam in front of an entry's first MFMA those pads fall behind the
+// counted wait.  A ratio-stage consumer kSP128Dist ratio-stage instructions (five gaps or more) behind its producer always
+// has one of those seams in between and gets none of its own.
+constexpr int kSP128Dist = 24;
+// phase B gap (0 .. 31, gap g follows MFMA g): even gaps of entries 0 .. 3 carry an LDS-DMA piece, of entries 8 .. 15 an X load
+constexpr bool sp128_b_busy(int gap) { return (gap & 1) == 0 && ((gap >> 1) < 4 || (gap >> 1) >= 8); }
+struct SP128PhaseB {
+  int first[33];   // moved reciprocals first[g] .. first[g + 1] - 1 sit in gap g
+};
+constexpr SP128PhaseB sp128_phase_b(int rb) {
+  // round-robin from the fourth gap on: phase B's first MFMAs cover the XDL write -> VALU read distance of GEMM1's last, and
+  // the first reciprocal (it reads what an asm MFMA wrote) has the seam of entry 1 between itself and that MFMA.
+  // The gaps without a load first: one, then a second per odd gap (behind the og = 1 MFMA and the entry's LDS reads:
+  // the counted wait follows, so whatever hipcc pads in front of the next MFMA never touches a reciprocal), one, then a second
+  // per even gap of entries 4 .. 7; then one and a second per gap that carries a load; a third per odd gap (RB = 64 only)
+  int cnt[32] = {};
+  int left = rb;
+  for (int pass = 0; pass < 7; ++pass)
+    for (int g = 3; g < 32; ++g) {
+      const int cls = (g & 1) ? 0 : sp128_b_busy(g) ? 2 : 1;
+      if (left > 0 && cls == (pass == 6 ? 0 : pass >> 1)) ++cnt[g], --left;
+    }
+  SP128PhaseB t{};
+  for (int g = 0; g < 32; ++g) t.first[g + 1] = t.first[g] + cnt[g];
+  return t;
+}
+struct SP128PhaseA {
+  int first[33];   // instructions first[g] .. first[g + 1] - 1 of op[] sit in gap g
+  int op[160];     // kind * 64 + index: kind 0 = reciprocal of element x, 1 = multiply of element x, 2 = pack y
+};
+constexpr SP128PhaseA sp128_phase_a(int rb) {
+  SP128PhaseA t{};
+  int pos_r[64] = {}, pos_m[64] = {};
+  for (int x = 0; x < 64; ++x) pos_r[x] = -1000;   // (the moved ones: long done)
+  int nr = rb, nm = 0, nc = 0, pos = 0;
+  int cost_left = 2 * (64 - rb) + 64 + 32;
+  for (int g = 0; g < 32; ++g) {
+    t.first[g] = pos;
+    const bool flush = g == 31;
+    const int budget = (cost_left + (32 - g) - 1) / (32 - g);
+    int used = 0;
+    for (int c = 0; c < 2 && nr < 64 && used + 2 <= budget; ++c) {   // at most two reciprocals per gap
+      pos_r[nr] = pos;
+      t.op[pos++] = nr++;
+      used += 2;
+    }
+    while (nm < 64 && nm < nr && (flush || (used < budget && pos - pos_r[nm] >= kSP128Dist))) {
+      pos_m[nm] = pos;
+      t.op[pos++] = 64 + nm++;
+      ++used;
+    }
+    while (nc < 32 && 2 * nc + 1 < nm && (flush || (used < budget && pos - pos_m[2 * nc + 1] >= kSP128Dist))) {
+      t.op[pos++] = 128 + nc++;
+      ++used;
+    }
+    cost_left -= used;
+  }
+  t.first[32] = pos;
+  return t;
+}
+template <int RB>
+inline constexpr SP128PhaseA kSP128TabA = sp128_phase_a(RB);
+template <int RB>
+inline constexpr SP128PhaseB kSP128TabB = sp128_phase_b(RB);
+
+template <int OPT, int RB>
 __global__ void __launch_bounds__(256, 1) sp128_kernel(const FusedArgs a) {
   using C = SP128Cfg<OPT>;
+  static_assert(RB >= 0 && RB <= 64 && RB % 16 == 0, "whole S tiles' worth of units");
   constexpr int R_PAD = C::R_PAD, KS = C::KS, RT = C::RT, ROWB = C::ROWB, IMG = C::IMG, PF = C::PF, N1 = C::N1, N2 = C::N2;
   using u32x2 = __attribute__((ext_vector_type(2))) uint32_t;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -200,6 +280,43 @@ __global__ void __launch_bounds__(256, 1) sp128_kernel(const FusedArgs a) {
         asm volatile("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(g2) : "v"(e0), "v"(e1));
       }
     };
+    // RB > 0: the same three instructions per element, in place on the S register, addressed by the tables' element x /
+    // pack y (unit order above); tile in S[sb] / xb[sb]
+    auto rcp_x = [&](auto xc, auto sbc) {
+      constexpr int x = decltype(xc)::value, sb = decltype(sbc)::value, u = x >> 2, pos = x & 3;
+      constexpr int tt = u >> 3, og = (u >> 2) & 1, d = 2 * (u & 3);
+      float r = S[sb][og][tt][2 * d + pos];
+      asm volatile("v_rcp_f32 %0, %0" : "+v"(r));
+      S[sb][og][tt][2 * d + pos] = r;
+    };
+    auto mul_x = [&](auto xc, auto sbc) {
+      constexpr int x = decltype(xc)::value, sb = decltype(sbc)::value, u = x >> 2, p = x & 3;
+      constexpr int tt = u >> 3, og = (u >> 2) & 1, d = 2 * (u & 3);
+      float r = S[sb][og][tt][2 * d + p];
+      const uint32_t w = xb[sb][og][2 * tt + (d >> 2)][(d & 3) + (p >> 1)];
+      if constexpr ((p & 1) == 0) asm volatile("v_fma_mix_f32 %0, %1, %0, 0 op_sel_hi:[1,0,0]" : "+v"(r) : "v"(w));
+      else asm volatile("v_fma_mix_f32 %0, %1, %0, 0 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(r) : "v"(w));
+      S[sb][og][tt][2 * d + p] = r;
+    };
+    auto pack_y = [&](auto yc, auto sbc) {
+      constexpr int y = decltype(yc)::value, sb = decltype(sbc)::value, u = y >> 1, h = y & 1;
+      constexpr int tt = u >> 3, og = (u >> 2) & 1, d = 2 * (u & 3);
+      uint32_t& g2 = gn[og][tt][d + h];
+      const float e0 = S[sb][og][tt][2 * d + 2 * h], e1 = S[sb][og][tt][2 * d + 2 * h + 1];
+      asm volatile("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(g2) : "v"(e0), "v"(e1));
+    };
+    auto table_op = [&](auto cc, auto sbc) {   // instruction cc of the phase A table
+      constexpr int code = kSP128TabA<RB>.op[decltype(cc)::value], kind = code >> 6;
+      using I = std::integral_constant<int, code & 63>;
+      if constexpr (kind == 0) rcp_x(I{}, sbc);
+      else if constexpr (kind == 1) mul_x(I{}, sbc);
+      else pack_y(I{}, sbc);
+    };
+    // the moved reciprocals of the tile in S[sb], gap `gap` of phase B
+    auto rcp_gap = [&](auto gapc, auto sbc) {
+      constexpr int gi = decltype(gapc)::value, lo = kSP128TabB<RB>.first[gi], n = kSP128TabB<RB>.first[gi + 1] - lo;
+      static_for<n>([&](auto cc) { rcp_x(std::integral_constant<int, lo + decltype(cc)::value>{}, sbc); });
+    };
     // the LDS reads of a stream entry into ring slot rs.  G1 entry k: tt = k & 1, kk = k >> 1; G2 entry k: rt = k % RT,
     // (tt, m2) = k / RT.  slotc = panel ring slot of the entry's tile.
     auto issue_g1 = [&](auto kc, auto slotc, auto rsc) {
@@ -244,8 +361,27 @@ __global__ void __launch_bounds__(256, 1) sp128_kernel(const FusedArgs a) {
     auto ratio_gap = [&](auto gapc, auto sbc) {
       constexpr int gi = decltype(gapc)::value, per = C::NEL / 32;
       static_assert(C::NEL % 32 == 0, "whole instructions per gap");
-      static_for<per>([&](auto cc) { ratio_op(std::integral_constant<int, gi * per + decltype(cc)::value>{}, sbc); });
+      if constexpr (RB == 0) {
+        static_for<per>([&](auto cc) { ratio_op(std::integral_constant<int, gi * per + decltype(cc)::value>{}, sbc); });
+      } else {
+        constexpr int lo = kSP128TabA<RB>.first[gi], n = kSP128TabA<RB>.first[gi + 1] - lo;
+        static_for<n>([&](auto cc) { table_op(std::integral_constant<int, lo + decltype(cc)::value>{}, sbc); });
+      }
     };
+    // per-phase clock sums (diagnostic builds only: -DNMFMU_SP128_PHASE_STAMPS; tools/sp128_phases.py).  Every boundary reads
+    // the shader clock and drains the LDS counter for it, so the build is for the split between the phases, not for timing.
+#ifdef NMFMU_SP128_PHASE_STAMPS
+    unsigned long long ph_sum[2] = {0, 0}, ph_last = __builtin_amdgcn_s_memtime();
+    auto phase_end = [&](int which) {   // the phase that ends here: 0 = A, 1 = B
+      const unsigned long long c = __builtin_amdgcn_s_memtime();
+      ph_sum[which] += c - ph_last;
+      ph_last = c;
+    };
+    auto phase_reset = [&]() { ph_last = __builtin_amdgcn_s_memtime(); };
+#else
+    auto phase_end = [&](int) {};
+    auto phase_reset = [&]() {};
+#endif
 
     // ---- one group of four tiles i0 .. i0+3 (i0 a multiple of 4: ring slot = it, S / X buffer = it & 1)
     auto group = [&](int i0, auto lastc) {
@@ -265,13 +401,24 @@ __global__ void __launch_bounds__(256, 1) sp128_kernel(const FusedArgs a) {
         using OG0 = std::integral_constant<int, 0>;
         using OG1 = std::integral_constant<int, 1>;
         if constexpr (final_it && e.k == 0)   // last tile: no GEMM1 to hide the ratio stage behind
-          static_for<C::NEL>([&](auto kc) { ratio_op(kc, SB{}); });
+          static_for<C::NEL - RB>([&](auto kc) {
+            if constexpr (RB == 0) ratio_op(kc, SB{});
+            else table_op(kc, SB{});
+          });
+        if constexpr (e.k == 0) phase_end(e.g1 || final_it ? 1 : 0);
+        if constexpr (RB > 0 && e.g1 && e.k == 0) {
+          // (RB > 0: the scalar upkeep sits at the seam in front of the entry's first MFMA, never between its two MFMAs --
+          // hipcc's own instructions and the pads it owes the MFMA chains then fall behind a counted wait, not a ratio op)
+          dsrc = panel_src(i0 + e.it + 3);
+          xs0 = x_src(i0 + e.it + 2, 0);
+          xs1 = x_src(i0 + e.it + 2, 1);
+        }
         asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(sp_younger<N1, N2, PF>(n, last)));
         if constexpr (e.g1) {
           // ---- phase A(it): GEMM1 of tile i0+it+1, ratio stage of tile i0+it
           using NB = std::integral_constant<int, (e.it + 1) & 1>;
           mfma_g1(K{}, NB{}, RS{}, OG0{});
-          if constexpr (e.k == 0) {
+          if constexpr (RB == 0 && e.k == 0) {
             dsrc = panel_src(i0 + e.it + 3);
             xs0 = x_src(i0 + e.it + 2, 0);
             xs1 = x_src(i0 + e.it + 2, 1);
@@ -293,9 +440,13 @@ __global__ void __launch_bounds__(256, 1) sp128_kernel(const FusedArgs a) {
             if constexpr (e.k < C::NPW) dma_piece(dsrc, K{}, std::integral_constant<int, (e.it + 3) & 3>{});
             if constexpr (e.k >= 8 && e.k < 12) load_x1(xs0, xb[e.it & 1][0], std::integral_constant<int, e.k - 8>{});
             if constexpr (e.k >= 12) load_x1(xs1, xb[e.it & 1][1], std::integral_constant<int, e.k - 12>{});
+            // the first RB reciprocals of tile i0+it+1, in place in S[(it + 1) & 1] (phase B(3) serves the next group's tile 0)
+            if constexpr (RB > 0) rcp_gap(std::integral_constant<int, 2 * e.k>{}, std::integral_constant<int, (e.it + 1) & 1>{});
           }
           mfma_g2(K{}, RS{}, OG1{});
           if constexpr (n + PF < LEN) issue_entry(std::integral_constant<int, n + PF>{}, lastc);
+          if constexpr (RB > 0 && !final_it)
+            rcp_gap(std::integral_constant<int, 2 * e.k + 1>{}, std::integral_constant<int, (e.it + 1) & 1>{});
           if constexpr (!final_it && e.k == N2 - 1) {
             // X(i0+it+1) has landed: at most this iteration's 4 panel pieces + 8 X loads stay in flight
             wait_x(std::integral_constant<int, 12>{}, xb[(e.it + 1) & 1]);
@@ -338,11 +489,20 @@ __global__ void __launch_bounds__(256, 1) sp128_kernel(const FusedArgs a) {
         if constexpr (k + PF < N1) issue_g1(std::integral_constant<int, k + PF>{}, Z{}, std::integral_constant<int, k % PF>{});
       });
       asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");   // XDL write -> VALU read of S (asm MFMAs are not padded)
+      static_for<RB>([&](auto xc) { rcp_x(xc, Z{}); });       // tile 0's share of phase B(-1)
     }
     stamp(0);
+    phase_reset();
     int i0 = 0;
     for (; i0 + 4 < nt; i0 += 4) group(i0, std::false_type{});
     group(i0, std::true_type{});
+    phase_end(1);
+#ifdef NMFMU_SP128_PHASE_STAMPS
+    if (a.debug && wave == 0 && blockIdx.x == 0 && lane == 0) {   // [16] phase A cycles (nt - 1 phases), [17] phase B cycles (nt)
+      unsigned long long* dbg = reinterpret_cast<unsigned long long*>(a.debug);
+      dbg[16] = ph_sum[0], dbg[17] = ph_sum[1], dbg[18] = (unsigned long long)nt;
+    }
+#endif
     stamp(1);
     // XDL write -> VALU read of the accumulators; the clamped tail prefetches: nothing may land in LDS / registers after this
     asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
@@ -523,14 +683,16 @@ __global__ void __launch_bounds__(256, 1) sp128_kernel(const FusedArgs a) {
   stamp(3);
 }
 
-template <int OPT>
+template <int OPT, int RB>
 int launch_sp128_one(const FusedArgs& a, int grid, hipStream_t s) {
   using C = SP128Cfg<OPT>;
-  return launch_with_dynamic_lds<sp128_kernel<OPT>, C::THREADS, C::LDS_BYTES>(dim3(grid), s, a);
+  return launch_with_dynamic_lds<sp128_kernel<OPT, RB>, C::THREADS, C::LDS_BYTES>(dim3(grid), s, a);
 }
 
 // Host-side launcher (nmfmu_inst_sp128.hip).  Serves beta == 1, fp16 operands and target, padded rank 128, 256-row tiles.
 int launch_sp128(int r_pad, int opt, const FusedArgs& a, int grid, hipStream_t s);
+// ... the RB = 0 schedule, kept as the A/B arm of NMFMU_STAGE_DMA_SP128_RB0 (nmfmu_inst_sp128_rb0.hip)
+int launch_sp128_rb0(int r_pad, int opt, const FusedArgs& a, int grid, hipStream_t s);
 bool sp128_available(int r_pad, int opt, int mode);
 
 }  // namespace nmfmu

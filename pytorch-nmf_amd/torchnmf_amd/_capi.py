@@ -25,6 +25,8 @@ STAGE_DMA_LDSTR = 4         # ping-pong MU half-step at padded rank 128: one pan
                             # nothing reads or refreshes the factors' transposed images (include/nmfmu.h)
 STAGE_DMA_SP128 = 5         # as STAGE_DMA_LDSTR; the 'f16' MU half-step at padded rank 128 on the software-pipelined four-wave
                             # kernel with 64 owner rows per wave (csrc/nmfmu_sp128.h)
+STAGE_DMA_SP128_RB0 = 6     # as STAGE_DMA_SP128 with the kernel's whole ratio stage in phase A (RB = 0 in csrc/nmfmu_sp128.h): the
+                            # other arm of an A/B against the shipped placement, bit-identical results
 BETA_KL, BETA_EUC, BETA_IS, BETA_GEN = 0, 1, 2, 3
 KERNEL_FUSED, KERNEL_PP, KERNEL_SP = 0, 1, 2
 

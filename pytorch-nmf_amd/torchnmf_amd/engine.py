@@ -619,8 +619,11 @@ class DenseMU(AsyncLossMixin):
             steps = (self.step_h, self.step_w)
             if all(st.block_rows == 256 and (st.owner.rows_pad // 256) * st.nsplit >= ncu
                    and (st.panel.rows_pad // 64) % (4 * st.nsplit) == 0 for st in steps):
+                # TORCHNMF_AMD_SP128=rb0: the same kernel with its whole ratio stage in phase A (the other arm of the A/B of
+                # profiles/r09_sp128_respace_ab.md; bit-identical results)
+                rb0 = os.environ.get('TORCHNMF_AMD_SP128', '1') == 'rb0'
                 for st in steps:
-                    st.struct.stage = _capi.STAGE_DMA_SP128
+                    st.struct.stage = _capi.STAGE_DMA_SP128_RB0 if rb0 else _capi.STAGE_DMA_SP128
         self.gm = self.be.gram_alloc(self.r_pad, dev) if self.gram_path else None
         self.timer: Optional[KernelTimer] = None   # bench.py: times the fused launches live
         self.refresh_images()
