@@ -15,14 +15,18 @@
 #include "nmfmu_sp2.h"
 #include "nmfmu_sp128.h"
 
+// A/B build switches (tools/sp_bitcompare.py, pp_timeline.py, xb_timeline.py build with them); each is read in one place below
 #ifndef NMFMU_SP
-#define NMFMU_SP 1   // (A/B switch of round 6; 0 = padded rank 256, beta == 1, fp16 stays on the four-wave kernel)
+#define NMFMU_SP 1   // 0 = padded rank 256, beta == 1, fp16 stays on the four-wave kernel
 #endif
 #ifndef NMFMU_SP2
-#define NMFMU_SP2 1  // (A/B switch of round 6; 0 = padded rank 128, beta in {0, 0.5, 1.5, generic}, fp16 stays on the four-wave kernel)
+#define NMFMU_SP2 1  // 0 = padded rank 128, beta in {0, 0.5, 1.5, generic}, fp16 stays on the four-wave kernel
+#endif
+#ifndef NMFMU_PP_F16R
+#define NMFMU_PP_F16R 1   // 0 = the 3-byte target stays on the four-wave kernel at beta == 1 as well
 #endif
 #ifndef NMFMU_FUSE_APPLY_TWO_ACC
-#define NMFMU_FUSE_APPLY_TWO_ACC 1   // (A/B switch of round 3; 0 = beta != 1 always goes through slabs + the apply kernel)
+#define NMFMU_FUSE_APPLY_TWO_ACC 1   // 0 = beta != 1 always goes through slabs + the apply kernel
 #endif
 
 using namespace nmfmu;
@@ -34,54 +38,117 @@ inline bool is_f16(int precision) {   // fp16 operand images
   return precision == NMFMU_PREC_F16 || precision == NMFMU_PREC_F16X || precision == NMFMU_PREC_F16R;
 }
 inline bool x_is_f32(int precision) { return precision == NMFMU_PREC_BF16X3 || precision == NMFMU_PREC_F16X; }
+inline bool valid_block_rows(int block_rows) { return block_rows == 128 || block_rows == 256; }
+inline int workgroups(int owner_rows_pad, int block_rows, int nsplit) { return (owner_rows_pad / block_rows) * nsplit; }
+// the stages whose caller promises that nobody reads the factors' transposed images (include/nmfmu.h)
+inline bool one_image_stage(int stage) {
+  return stage == NMFMU_STAGE_DMA_LDSTR || stage == NMFMU_STAGE_DMA_SP128 || stage == NMFMU_STAGE_DMA_SP128_RB0;
+}
 
 // Diagnostic builds only (make EXTRA=-DNMFMU_DEBUG_HOOKS): NMFMU_FORCE_NSPLIT overrides the contraction split and
-// nmfmu_debug_set_buffer registers the clock-stamp buffer of the ping-pong kernel (tools/pp_timeline.py).  The product
-// library reads no environment variable and keeps no global state.
+// nmfmu_debug_set_buffer registers the clock-stamp buffer of the pipelined kernels (tools/pp_timeline.py) and of the streaming
+// kernel (tools/xb_timeline.py).  The product library reads no environment variable and keeps no global state.
 #ifdef NMFMU_DEBUG_HOOKS
-static int env_int(const char* name, int dflt) {
-  const char* v = std::getenv(name);
-  return v && *v ? std::atoi(v) : dflt;
+void* g_pp_debug = nullptr;
+void* debug_buffer() { return g_pp_debug; }
+int debug_set_buffer(void* buf) {
+  g_pp_debug = buf;
+  return NMFMU_OK;
 }
-static void* g_pp_debug = nullptr;
+int forced_nsplit() {   // (read once)
+  static const int forced = [] { const char* v = std::getenv("NMFMU_FORCE_NSPLIT"); return v && *v ? std::atoi(v) : 0; }();
+  return forced;
+}
+#else
+void* debug_buffer() { return nullptr; }
+int debug_set_buffer(void*) { return NMFMU_ERR_UNSUPPORTED; }
+int forced_nsplit() { return 0; }
 #endif
-#ifndef NMFMU_PP_F16R
-#define NMFMU_PP_F16R 1   // 0: the 3-byte target stays on the four-wave kernel at beta == 1 as well (A/B builds)
-#endif
-// which half-steps the ping-pong kernel serves: beta == 1, one operand plane (bf16 or fp16; fp16 with the 3-byte target),
-// padded rank <= 128
-static bool pp_eligible(int r_pad, int precision, float beta) {
-  return nmfmu_beta_kind(beta) == NMFMU_BETA_KL && r_pad <= 128 &&
-         (precision == NMFMU_PREC_F16 || precision == NMFMU_PREC_BF16 || (NMFMU_PP_F16R && precision == NMFMU_PREC_F16R));
+
+// Which kernel serves a dense half-step, and everything the rest of this file needs to know about that choice.
+enum Kernel { kFused, kPP, kSP, kSP2, kSP128 };   // four-wave fused | eight-wave ping-pong | nmfmu_sp.h | nmfmu_sp2.h | nmfmu_sp128.h
+struct Selection {
+  int stage_err;   // the stage does not go with this step: refused before the step's arguments are looked at
+  int err;         // no kernel serves the combination: refused after they are
+  int mode;        // the mode the kernel runs in (kModeMU of a split panel: kModeMU2)
+  Kernel kernel;
+  bool rb0;        // kSP128: its RB = 0 schedule (A/B arm)
+  bool trl;        // kPP: the instance that builds the transposed panel tile in LDS
+  int group;       // the tile loop runs in groups of this many tiles: tiles_per_split is rounded up to it
+  int wg_per_cu;   // workgroups a CU holds (the split rule fills the chip once)
+  bool owner_p2;   // the owner's transposed image is written (false: nobody reads it, epilogue and apply kernel skip it)
+};
+
+// Pure: a function of its arguments and of which instances the kernel units hold.
+Selection select_kernel(int r_pad, int precision, float beta, int block_rows, int stage, int mode, bool riding_loss) {
+  const int kind = nmfmu_beta_kind(beta);
+  const bool kl = kind == NMFMU_BETA_KL, f16 = precision == NMFMU_PREC_F16;
+  // ping-pong kernel: beta == 1, one operand plane (bf16 or fp16; fp16 with the 3-byte target), padded rank <= 128 ...
+  const bool pp = kl && r_pad <= 128 && (f16 || precision == NMFMU_PREC_BF16 || (NMFMU_PP_F16R && precision == NMFMU_PREC_F16R));
+  // ... of those, the ones with the instance that builds the transposed panel tile in LDS (NMFMU_STAGE_DMA_LDSTR) ...
+  const bool pp_trl = pp && pp_trl_available(r_pad, is_f16(precision) ? kOpF16 : kOpBf16, kModeMU);
+  // ... and of those, the ones NMFMU_STAGE_DMA_SP128 moves to the software-pipelined kernel with 64 owner rows per wave
+  const bool sp128 = pp_trl && f16 && sp128_available(r_pad, kOpF16, kModeMU);
+  // one wave per SIMD, software-pipelined, fp16 operands and target: beta == 1 at padded rank 256 (configs[4]'s shard), and
+  // the two-accumulator sibling for beta != 1 and != 2 at padded rank 128 (configs[2]'s beta < 1 legs)
+  const bool sp = NMFMU_SP && kl && r_pad == 256 && f16;
+  const bool sp2 = NMFMU_SP2 && (kind == NMFMU_BETA_IS || kind == NMFMU_BETA_GEN) && r_pad == 128 && f16;
+  const bool one_image = one_image_stage(stage), sp128_stage = one_image && stage != NMFMU_STAGE_DMA_LDSTR;
+
+  Selection s{};
+  s.mode = mode, s.kernel = kFused, s.group = 1, s.wg_per_cu = block_rows == 128 ? 2 : 1;
+  s.owner_p2 = !one_image && !(stage == NMFMU_STAGE_DMA_NOP2 && sp);
+  if (stage != NMFMU_STAGE_DMA && stage != NMFMU_STAGE_DMA_SPLIT && stage != NMFMU_STAGE_DMA_NOP2 && !one_image) {
+    s.stage_err = NMFMU_ERR_UNSUPPORTED;   // (register staging: no longer built)
+  } else if (one_image && mode != kModeLoss && (mode != kModeMU || block_rows != 256 || !pp_trl)) {
+    s.stage_err = NMFMU_ERR_UNSUPPORTED;   // one panel image: the ping-pong kernel's MU half-step only (the loss reads p1 alone anyway)
+  } else if (sp128_stage && !sp128) {
+    s.stage_err = NMFMU_ERR_UNSUPPORTED;
+  } else if (stage == NMFMU_STAGE_DMA_SPLIT && mode == kModeMU && precision != NMFMU_PREC_BF16X3) {
+    // split panel (PLCA: p1 = the Z-scaled factor, p2 = the unscaled one): the instantiation that stages BOTH images
+    if (kl && block_rows == 128) s.mode = kModeMU2;
+    else s.stage_err = NMFMU_ERR_UNSUPPORTED;
+  }
+  if (block_rows == 256) {   // the eight-wave ping-pong kernel; both half-steps (the apply is fused there as well)
+    if (mode == kModeDen || !pp) s.err = NMFMU_ERR_UNSUPPORTED;
+    s.kernel = kPP, s.group = 2;   // its tile loop is unrolled by two
+    s.trl = one_image && mode != kModeLoss;
+    if (sp128_stage && mode == kModeMU && !riding_loss) {   // (the loss-carrying half-step stays on the ping-pong kernel)
+      s.kernel = kSP128, s.group = 4, s.rb0 = stage == NMFMU_STAGE_DMA_SP128_RB0;   // ring slot = tile & 3
+    }
+  } else if (s.mode == kModeMU && (sp || sp2)) {
+    s.kernel = sp ? kSP : kSP2, s.group = 4, s.wg_per_cu = 1;   // ring slot = tile & 3; one 512-register workgroup per CU
+  } else if (r_pad != 32 && r_pad != 64 && r_pad != 128 && r_pad != 256) {
+    s.err = NMFMU_ERR_UNSUPPORTED;
+  }
+  return s;
 }
-// ... and of those, the ones that have the instance which builds the transposed panel tile in LDS (NMFMU_STAGE_DMA_LDSTR)
-static bool pp_ldstr_eligible(int r_pad, int precision, float beta) {
-  return pp_eligible(r_pad, precision, beta) && pp_trl_available(r_pad, is_f16(precision) ? kOpF16 : kOpBf16, kModeMU);
+
+// The apply kernel's side of the one-image promise (see nmfmu.h): NMFMU_OK, or the code a one-image stage is refused with on
+// a step whose half-step could not keep it; *writes_p2: the owner's transposed images are written.  The apply kernel serves
+// every one-image stage alike, so the question is put for NMFMU_STAGE_DMA_LDSTR, not for the half-step's own kernel.
+int apply_image_rule(const nmfmu_step* st, bool* writes_p2) {
+  const bool one_image = one_image_stage(st->stage);
+  const Selection sel = select_kernel(st->r_pad, st->precision, st->beta, st->block_rows,
+                                      one_image ? NMFMU_STAGE_DMA_LDSTR : st->stage, kModeMU, false);
+  *writes_p2 = sel.owner_p2;
+  return one_image ? sel.stage_err : NMFMU_OK;
 }
-// ... and the MU half-steps NMFMU_STAGE_DMA_SP128 moves to the software-pipelined kernel with 64 owner rows per wave (nmfmu_sp128.h)
-static bool sp128_eligible(int r_pad, int precision, float beta) {
-  return pp_ldstr_eligible(r_pad, precision, beta) && precision == NMFMU_PREC_F16 && sp128_available(r_pad, kOpF16, kModeMU);
-}
-// which half-steps the software-pipelined one-wave-per-SIMD kernel serves (nmfmu_sp.h): beta == 1, fp16 operands and target,
-// padded rank 256 -- the kernel of configs[4]'s shard
-static bool sp_eligible(int r_pad, int precision, float beta) {
-  return NMFMU_SP && nmfmu_beta_kind(beta) == NMFMU_BETA_KL && r_pad == 256 && precision == NMFMU_PREC_F16;
-}
-// ... and its two-accumulator sibling (nmfmu_sp2.h): beta != 1 and != 2, fp16 operands and target, padded rank 128 -- the
-// kernel of configs[2]'s beta < 1 legs
-static bool sp2_eligible(int r_pad, int precision, float beta) {
-  const int k = nmfmu_beta_kind(beta);
-  return NMFMU_SP2 && (k == NMFMU_BETA_IS || k == NMFMU_BETA_GEN) && r_pad == 128 && precision == NMFMU_PREC_F16;
-}
+
 // beta -> kernel branch (nmfmu_fused.h: BetaKind): the public kinds plus the two rsqrt special cases of the generic one
-static int kernel_beta_kind(float beta) {
+int kernel_beta_kind(float beta) {
   if (beta == 0.5f) return kSqrt;
   if (beta == 1.5f) return kSqrt3;
   return nmfmu_beta_kind(beta);
 }
 
-struct GramRef {   // Gram matrix of the panel (nmfmu_gram_panel): fp32 matrix + 16-bit images with per-row scales
-  const float* gram;
+// "The workgroup owns whole rows": unsplit contraction, so a kernel that can may apply the update in its epilogue.
+// outputs: the caller also gave everything that epilogue writes (nmfmu_colsum_nparts asks about the split alone)
+bool owns_whole_rows(const nmfmu_step* st, bool outputs) {
+  return st->nsplit == 1 && (!outputs || (st->owner.f && st->owner.p2_hi && st->owner.colsum && st->owner.colsum_part));
+}
+
+struct GramRef {   // Gram matrix of the panel (nmfmu_gram_panel): its 16-bit images with per-row scales
   const void* hi;
   const void* lo;
   const float* scale;
@@ -92,22 +159,11 @@ int fused_dispatch(const nmfmu_step* st, int mode, float* loss_part, int M, int 
   if (!st || !st->owner.p1_hi || !st->panel.p1_hi) return NMFMU_ERR_ARG;
   if (!st->xp && (mode == kModeMU || mode == kModeXB)) return NMFMU_ERR_ARG;   // (the denominator-only pass and the loss may run without a target)
   if (st->owner.rows_pad % kRowPad || st->panel.rows_pad % kRowPad) return NMFMU_ERR_ARG;
-  if (st->block_rows != 128 && st->block_rows != 256) return NMFMU_ERR_ARG;
-  if (st->stage != NMFMU_STAGE_DMA && st->stage != NMFMU_STAGE_DMA_SPLIT && st->stage != NMFMU_STAGE_DMA_NOP2 &&
-      st->stage != NMFMU_STAGE_DMA_LDSTR && st->stage != NMFMU_STAGE_DMA_SP128 && st->stage != NMFMU_STAGE_DMA_SP128_RB0)
-    return NMFMU_ERR_UNSUPPORTED;   // (register staging: no longer built)
-  // one panel image, the transposed tile built in LDS: the ping-pong kernel's MU half-step only (the loss reads p1 alone anyway)
-  const bool sp128_rb0 = st->stage == NMFMU_STAGE_DMA_SP128_RB0;   // (the same kernel on its RB = 0 schedule: A/B arm)
-  const bool sp128 = st->stage == NMFMU_STAGE_DMA_SP128 || sp128_rb0;
-  const bool ldstr = (st->stage == NMFMU_STAGE_DMA_LDSTR || sp128) && mode != kModeLoss;
-  if (ldstr && (mode != kModeMU || st->block_rows != 256 || !pp_ldstr_eligible(st->r_pad, st->precision, st->beta)))
-    return NMFMU_ERR_UNSUPPORTED;
-  if (sp128 && !sp128_eligible(st->r_pad, st->precision, st->beta)) return NMFMU_ERR_UNSUPPORTED;
-  // split panel (PLCA: p1 = the Z-scaled factor, p2 = the unscaled one): the instantiation that stages BOTH images
-  if (st->stage == NMFMU_STAGE_DMA_SPLIT && mode == kModeMU && !(st->precision == NMFMU_PREC_BF16X3)) {
-    if (nmfmu_beta_kind(st->beta) != NMFMU_BETA_KL || st->block_rows != 128) return NMFMU_ERR_UNSUPPORTED;
-    mode = kModeMU2;
-  }
+  if (!valid_block_rows(st->block_rows)) return NMFMU_ERR_ARG;
+  const Selection sel = select_kernel(st->r_pad, st->precision, st->beta, st->block_rows, st->stage, mode,
+                                      /*riding loss*/ mode == kModeMU && loss_part != nullptr);
+  if (sel.stage_err) return sel.stage_err;
+  mode = sel.mode;
   if (st->r_pad != pad_rank(st->rank) || st->nsplit < 1) return NMFMU_ERR_ARG;
   const bool x3 = st->precision == NMFMU_PREC_BF16X3;
   if (x3 && (!st->owner.p1_lo || !st->panel.p1_lo)) return NMFMU_ERR_ARG;
@@ -115,21 +171,13 @@ int fused_dispatch(const nmfmu_step* st, int mode, float* loss_part, int M, int 
   if (st->precision == NMFMU_PREC_F16R && kind == NMFMU_BETA_EUC) return NMFMU_ERR_UNSUPPORTED;   // the target is an operand there: F16X
   FusedArgs a{};
   a.xp = st->xp;
-  a.p1_hi = static_cast<const uint16_t*>(st->panel.p1_hi);
-  a.p1_lo = static_cast<const uint16_t*>(st->panel.p1_lo);
-  a.p2_hi = static_cast<const uint16_t*>(st->panel.p2_hi);
-  a.p2_lo = static_cast<const uint16_t*>(st->panel.p2_lo);
-  a.a1_hi = static_cast<const uint16_t*>(st->owner.p1_hi);
-  a.a1_lo = static_cast<const uint16_t*>(st->owner.p1_lo);
-  a.slab_num = st->slab_num;
-  a.slab_den = st->slab_den;
-  a.loss_part = loss_part;
-  a.M = M;
-  a.K = K;
-  a.M_pad = st->owner.rows_pad;
-  a.ktiles = st->panel.rows_pad / kBK;
-  a.nsplit = st->nsplit;
-  a.tiles_per_split = (a.ktiles + st->nsplit - 1) / st->nsplit;
+  a.p1_hi = static_cast<const uint16_t*>(st->panel.p1_hi), a.p1_lo = static_cast<const uint16_t*>(st->panel.p1_lo);
+  a.p2_hi = static_cast<const uint16_t*>(st->panel.p2_hi), a.p2_lo = static_cast<const uint16_t*>(st->panel.p2_lo);
+  a.a1_hi = static_cast<const uint16_t*>(st->owner.p1_hi), a.a1_lo = static_cast<const uint16_t*>(st->owner.p1_lo);
+  a.slab_num = st->slab_num, a.slab_den = st->slab_den, a.loss_part = loss_part;
+  a.M = M, a.K = K, a.M_pad = st->owner.rows_pad;
+  a.ktiles = st->panel.rows_pad / kBK, a.nsplit = st->nsplit;
+  a.tiles_per_split = ((a.ktiles + st->nsplit - 1) / st->nsplit + sel.group - 1) / sel.group * sel.group;
   a.beta = st->beta;
   a.status = st->status;
   a.cs_owner = st->owner.colsum;   // fp16 operands, beta < 1: typical S -> scale of Gn / Gp (nmfmu_fused.h)
@@ -140,7 +188,7 @@ int fused_dispatch(const nmfmu_step* st, int mode, float* loss_part, int M, int 
     a.f = st->owner.f;
     a.kl_den = fuse_kl_den;
     a.o1_hi = static_cast<uint16_t*>(st->owner.p1_hi), a.o1_lo = static_cast<uint16_t*>(st->owner.p1_lo);
-    a.o2_hi = static_cast<uint16_t*>(st->owner.p2_hi), a.o2_lo = static_cast<uint16_t*>(st->owner.p2_lo);
+    a.o2_hi = sel.owner_p2 ? static_cast<uint16_t*>(st->owner.p2_hi) : nullptr, a.o2_lo = static_cast<uint16_t*>(st->owner.p2_lo);
     a.colsum_part = st->owner.colsum_part;
     a.l1 = st->l1, a.l2 = st->l2, a.gamma = st->gamma;
   }
@@ -164,46 +212,29 @@ int fused_dispatch(const nmfmu_step* st, int mode, float* loss_part, int M, int 
   } else if (!loss_part) {
     return NMFMU_ERR_ARG;
   }
-  const int grid = (st->owner.rows_pad / st->block_rows) * st->nsplit;
-  if (st->block_rows == 256) {   // the eight-wave ping-pong kernel (beta == 1, one operand plane, padded rank <= 128)
-    if (!st->xp || mode == kModeDen || !pp_eligible(st->r_pad, st->precision, st->beta)) return NMFMU_ERR_UNSUPPORTED;
-    a.tiles_per_split = (a.tiles_per_split + 1) & ~1;   // its tile loop is unrolled by two
-    a.debug = mode == kModeMU ? st->stamps : nullptr;
-#ifdef NMFMU_DEBUG_HOOKS
-    if (mode == kModeMU && g_pp_debug) a.debug = g_pp_debug;
-#endif
-    if (ldstr) a.o2_hi = nullptr;   // nobody reads the owner's transposed image: the fused apply skips it
-    if (sp128 && mode == kModeMU && !loss_part) {   // (the loss-carrying half-step stays on the ping-pong kernel)
-      a.tiles_per_split = (a.tiles_per_split + 3) & ~3;   // its tile loop runs in groups of four (ring slot = tile & 3)
-      return sp128_rb0 ? launch_sp128_rb0(st->r_pad, kOpF16, a, grid, s) : launch_sp128(st->r_pad, kOpF16, a, grid, s);
-    }
-    return launch_pp(st->r_pad, is_f16(st->precision) ? kOpF16 : kOpBf16, mode, a, grid, s, st->precision == NMFMU_PREC_F16R,
-                     /*riding loss*/ mode == kModeMU && loss_part != nullptr, ldstr);
+  if (sel.err || (sel.kernel == kPP && !st->xp)) return NMFMU_ERR_UNSUPPORTED;   // (the ping-pong kernel's loss pass needs the target)
+  const int grid = workgroups(st->owner.rows_pad, st->block_rows, st->nsplit);
+  // clock stamps (nmfmu_step.stamps) of the pipelined kernels' MU half-step; diagnostic builds: the registered buffer there
+  // and on the streaming kernel
+  const bool stamped = mode == kModeMU && (sel.kernel == kPP || sel.kernel == kSP128 || sel.kernel == kSP);
+  a.debug = stamped ? st->stamps : nullptr;
+  if (debug_buffer() && (stamped || (sel.kernel == kFused && mode == kModeXB))) a.debug = debug_buffer();
+  const int opt = is_f16(st->precision) ? kOpF16 : kOpBf16, kk = kernel_beta_kind(st->beta);
+  switch (sel.kernel) {
+    case kSP128: return sel.rb0 ? launch_sp128_rb0(st->r_pad, kOpF16, a, grid, s) : launch_sp128(st->r_pad, kOpF16, a, grid, s);
+    case kPP:
+      return launch_pp(st->r_pad, opt, mode, a, grid, s, st->precision == NMFMU_PREC_F16R,
+                       /*riding loss*/ mode == kModeMU && loss_part != nullptr, sel.trl);
+    case kSP: return launch_sp(st->r_pad, kOpF16, a, grid, s);
+    case kSP2: return launch_sp2(st->r_pad, kk, a, grid, s);
+    case kFused: break;
   }
-  if (mode == kModeMU && sp_eligible(st->r_pad, st->precision, st->beta)) {
-    a.tiles_per_split = (a.tiles_per_split + 3) & ~3;   // its tile loop runs in groups of four (ring slot = tile & 3)
-    a.debug = st->stamps;
-#ifdef NMFMU_DEBUG_HOOKS
-    if (g_pp_debug) a.debug = g_pp_debug;
-#endif
-    if (st->stage == NMFMU_STAGE_DMA_NOP2) a.o2_hi = nullptr;   // nobody reads the owner's transposed image: the epilogue skips it
-    return launch_sp(st->r_pad, kOpF16, a, grid, s);
-  }
-  if (mode == kModeMU && sp2_eligible(st->r_pad, st->precision, st->beta)) {
-    a.tiles_per_split = (a.tiles_per_split + 3) & ~3;
-    return launch_sp2(st->r_pad, kernel_beta_kind(st->beta), a, grid, s);
-  }
-  const int kk = kernel_beta_kind(st->beta);
-#ifdef NMFMU_DEBUG_HOOKS
-  a.debug = mode == kModeXB ? g_pp_debug : nullptr;   // per-workgroup phase stamps of the streaming kernel (tools/xb_timeline.py)
-#endif
   switch (st->r_pad) {
     case 32: return launch_fused_r32(kk, st->precision, mode, a, grid, s);
     case 64: return launch_fused_r64(kk, st->precision, mode, a, grid, s);
     case 128: return launch_fused_r128(kk, st->precision, mode, a, grid, s);
-    case 256: return launch_fused_r256(kk, st->precision, mode, a, grid, s);
+    default: return launch_fused_r256(kk, st->precision, mode, a, grid, s);
   }
-  return NMFMU_ERR_UNSUPPORTED;
 }
 
 struct Timer {
@@ -238,53 +269,47 @@ int nmfmu_supported(int r_pad, int precision) {
 }
 
 int nmfmu_block_rows(int r_pad, int precision, float beta) {
-  // beta == 1 with one operand plane and padded rank <= 128: the eight-wave ping-pong kernel on 256-row tiles.
-  // Everything else: the four-wave kernel on 128-row tiles (two workgroups per CU where the registers allow).
-  return pp_eligible(r_pad, precision, beta) ? 256 : 128;
-}
-
-int nmfmu_choose_nsplit(int owner_rows_pad, int panel_rows_pad, int block_rows, int num_cu) {
-  if (owner_rows_pad <= 0 || panel_rows_pad <= 0 || (block_rows != 128 && block_rows != 256)) return NMFMU_ERR_ARG;
-  const int mblocks = owner_rows_pad / block_rows;
-  const int ktiles = panel_rows_pad / kBK;
-#ifdef NMFMU_DEBUG_HOOKS
-  static const int forced = env_int("NMFMU_FORCE_NSPLIT", 0);
-  if (forced > 0) return std::min(forced, std::max(1, ktiles));
-#endif
-  // 128-row tiles run two workgroups per CU (both wave slots of every SIMD); 256-row tiles run one.
-  const int target = (block_rows == 128 ? 2 : 1) * std::max(num_cu, 1);
-  int ns = (target + mblocks - 1) / mblocks;
-  if (ns > 8) ns = (ns + 7) / 8 * 8;           // same-chunk workgroups then share an XCD (block b runs on XCD b % 8)
-  ns = std::min(ns, std::max(1, ktiles / 4));  // at least 4 tiles per workgroup to amortise prologue/epilogue
-  return std::max(ns, 1);
-}
-
-int nmfmu_kernel_family(int r_pad, int precision, float beta) {
-  if (pp_eligible(r_pad, precision, beta)) return NMFMU_KERNEL_PP;
-  if (sp_eligible(r_pad, precision, beta) || sp2_eligible(r_pad, precision, beta)) return NMFMU_KERNEL_SP;
-  return NMFMU_KERNEL_FUSED;
-}
-
-int nmfmu_pp_lds_transpose_supported(int r_pad, int precision, float beta) { return pp_ldstr_eligible(r_pad, precision, beta) ? 1 : 0; }
-
-int nmfmu_choose_nsplit_for(int owner_rows_pad, int panel_rows_pad, int r_pad, int precision, float beta, int block_rows, int num_cu) {
-  if (owner_rows_pad <= 0 || panel_rows_pad <= 0 || (block_rows != 128 && block_rows != 256)) return NMFMU_ERR_ARG;
-  if (block_rows == 128 && (sp_eligible(r_pad, precision, beta) || sp2_eligible(r_pad, precision, beta))) {
-    // one 512-register workgroup per CU: as many splits as fill the chip ONCE (whole rounds when the row blocks alone
-    // exceed it), each a multiple of four tiles
-    const int mblocks = owner_rows_pad / 128, ktiles = panel_rows_pad / kBK;
-    int ns = (std::max(num_cu, 1) + mblocks - 1) / mblocks;
-    ns = std::min(ns, std::max(1, ktiles / 8));
-    return std::max(ns, 1);
-  }
-  return nmfmu_choose_nsplit(owner_rows_pad, panel_rows_pad, block_rows, num_cu);
+  // 256-row tiles where the eight-wave ping-pong kernel serves the MU half-step (beta == 1, one operand plane, padded rank
+  // <= 128).  Everything else: 128-row tiles (the four-wave kernels; two workgroups per CU where the registers allow).
+  return select_kernel(r_pad, precision, beta, 256, NMFMU_STAGE_DMA, kModeMU, false).err ? 128 : 256;
 }
 
 int nmfmu_step_block_rows(int owner_rows_pad, int panel_rows_pad, int r_pad, int precision, float beta, int num_cu) {
-  if (pp_eligible(r_pad, precision, beta)) return 256;   // both half-steps (the apply is fused there as well)
-  if (owner_rows_pad <= 0 || panel_rows_pad <= 0) return NMFMU_ERR_ARG;
   (void)num_cu;
-  return 128;                                              // four-wave kernel
+  const int block_rows = nmfmu_block_rows(r_pad, precision, beta);
+  if (block_rows == 128 && (owner_rows_pad <= 0 || panel_rows_pad <= 0)) return NMFMU_ERR_ARG;   // (not looked at for the ping-pong kernel)
+  return block_rows;
+}
+
+int nmfmu_kernel_family(int r_pad, int precision, float beta) {
+  const Kernel k = select_kernel(r_pad, precision, beta, nmfmu_block_rows(r_pad, precision, beta), NMFMU_STAGE_DMA, kModeMU, false).kernel;
+  return k == kPP ? NMFMU_KERNEL_PP : (k == kSP || k == kSP2) ? NMFMU_KERNEL_SP : NMFMU_KERNEL_FUSED;
+}
+
+int nmfmu_pp_lds_transpose_supported(int r_pad, int precision, float beta) {
+  return select_kernel(r_pad, precision, beta, 256, NMFMU_STAGE_DMA_LDSTR, kModeMU, false).stage_err ? 0 : 1;
+}
+
+// The split rule.  wg_per_cu == 2 (four-wave kernel on 128-row tiles: both wave slots of every SIMD) or 1 (256-row tiles);
+// pipelined: a one-wave-per-SIMD kernel, one 512-register workgroup per CU -- as many splits as fill the chip ONCE (whole
+// rounds when the row blocks alone exceed it), each at least two groups of four tiles
+static int split_rule(int owner_rows_pad, int panel_rows_pad, int block_rows, int num_cu, int wg_per_cu, bool pipelined) {
+  if (owner_rows_pad <= 0 || panel_rows_pad <= 0 || !valid_block_rows(block_rows)) return NMFMU_ERR_ARG;
+  const int mblocks = owner_rows_pad / block_rows, ktiles = panel_rows_pad / kBK;
+  if (const int forced = pipelined ? 0 : forced_nsplit(); forced > 0) return std::min(forced, std::max(1, ktiles));
+  int ns = (wg_per_cu * std::max(num_cu, 1) + mblocks - 1) / mblocks;
+  if (ns > 8 && !pipelined) ns = (ns + 7) / 8 * 8;   // same-chunk workgroups then share an XCD (block b runs on XCD b % 8)
+  ns = std::min(ns, std::max(1, ktiles / (pipelined ? 8 : 4)));   // at least 4 tiles per workgroup to amortise prologue/epilogue
+  return std::max(ns, 1);
+}
+
+int nmfmu_choose_nsplit(int owner_rows_pad, int panel_rows_pad, int block_rows, int num_cu) {
+  return split_rule(owner_rows_pad, panel_rows_pad, block_rows, num_cu, block_rows == 128 ? 2 : 1, false);
+}
+
+int nmfmu_choose_nsplit_for(int owner_rows_pad, int panel_rows_pad, int r_pad, int precision, float beta, int block_rows, int num_cu) {
+  const Selection sel = select_kernel(r_pad, precision, beta, block_rows, NMFMU_STAGE_DMA, kModeMU, false);
+  return split_rule(owner_rows_pad, panel_rows_pad, block_rows, num_cu, sel.wg_per_cu, sel.kernel == kSP || sel.kernel == kSP2);
 }
 
 size_t nmfmu_xp_bytes(int owner_rows_pad, int panel_rows_pad, int precision) {
@@ -298,7 +323,7 @@ size_t nmfmu_colsum_part_bytes(int rows_pad, int r_pad) { return (size_t)(rows_p
 
 int nmfmu_pack_x(const float* v, int64_t ld, int rows, int cols, int transpose, int precision, int block_rows, void* xp,
                  int owner_rows_pad, int panel_rows_pad, uint32_t* flags, void* stream) {
-  if (!v || !xp || rows <= 0 || cols <= 0 || (block_rows != 128 && block_rows != 256)) return NMFMU_ERR_ARG;
+  if (!v || !xp || rows <= 0 || cols <= 0 || !valid_block_rows(block_rows)) return NMFMU_ERR_ARG;
   const int m = transpose ? cols : rows, k = transpose ? rows : cols;
   if (owner_rows_pad != pad_rows(m) || panel_rows_pad != pad_rows(k)) return NMFMU_ERR_ARG;
   const int fmt = x_is_f32(precision) ? 1 : (precision == NMFMU_PREC_F16 ? 2 : (precision == NMFMU_PREC_F16R ? 3 : 0));
@@ -334,16 +359,28 @@ int nmfmu_pack_factor_scaled(const nmfmu_factor* fac, int rank, int r_pad, int p
   return pack_factor_common(fac, rank, r_pad, precision, scale, stream);
 }
 
-int nmfmu_mu_partial(const nmfmu_step* st, void* stream) {
+static int partial_sums(const nmfmu_step* st, int mode, void* stream) {
   if (!st) return NMFMU_ERR_ARG;
   if (!nmfmu_supported(st->r_pad, st->precision)) return NMFMU_ERR_UNSUPPORTED;
-  return fused_dispatch(st, kModeMU, nullptr, st->owner.rows, st->panel.rows, S(stream));
+  return fused_dispatch(st, mode, nullptr, st->owner.rows, st->panel.rows, S(stream));
 }
+int nmfmu_mu_partial(const nmfmu_step* st, void* stream) { return partial_sums(st, kModeMU, stream); }
+int nmfmu_den_partial(const nmfmu_step* st, void* stream) { return partial_sums(st, kModeDen, stream); }
 
-int nmfmu_den_partial(const nmfmu_step* st, void* stream) {
-  if (!st) return NMFMU_ERR_ARG;
-  if (!nmfmu_supported(st->r_pad, st->precision)) return NMFMU_ERR_UNSUPPORTED;
-  return fused_dispatch(st, kModeDen, nullptr, st->owner.rows, st->panel.rows, S(stream));
+// A complete MU half-step (phase 0), its fused launch alone (1) or what follows that launch (2).  xlogs_part: the launch is
+// the kernel instance that also accumulates the riding loss
+static int mu_step_common(const nmfmu_step* st, const float* kl_den, int phase, float* xlogs_part, void* stream) {
+  const bool kl = nmfmu_beta_kind(st->beta) == NMFMU_BETA_KL;
+  // apply in the fused kernel's epilogue (nmf.py:78-92) when the workgroup owns whole rows: beta == 1 (closed-form denominators)
+  // on both kernels, beta != 1 (two accumulator sets) on the four-wave kernel in the single-plane precisions up to rank pad 128
+  const bool fuse = owns_whole_rows(st, true) && (kl || (NMFMU_FUSE_APPLY_TWO_ACC && st->precision != NMFMU_PREC_BF16X3 && st->r_pad <= 128));
+  int e = 0;
+  if (phase != 2) e = fused_dispatch(st, kModeMU, xlogs_part, st->owner.rows, st->panel.rows, S(stream), kl_den, fuse);
+  if (e || phase == 1) return e;
+  // what is left: the column-sum finalize, or the whole apply
+  return fuse ? launch_colsum_finalize(st->owner.colsum_part, workgroups(st->owner.rows_pad, st->block_rows, 1), st->r_pad,
+                                       st->owner.colsum, S(stream))
+              : nmfmu_mu_apply(st, nullptr, nullptr, 0, kl ? kl_den : nullptr, stream);
 }
 
 int nmfmu_mu_step(const nmfmu_step* st, const float* kl_den, int phase, void* stream) {
@@ -352,30 +389,14 @@ int nmfmu_mu_step(const nmfmu_step* st, const float* kl_den, int phase, void* st
   // (a split panel -- images of two different matrices -- belongs to nmfmu_mu_partial: PLCA's EM reads the slabs; a complete
   // MU half-step of ONE panel matrix has nothing to split, and the fused-apply epilogue stages p1 only)
   if (st->stage == NMFMU_STAGE_DMA_SPLIT) return NMFMU_ERR_ARG;
-  const bool kl = nmfmu_beta_kind(st->beta) == NMFMU_BETA_KL;
-  if (kl && !kl_den) return NMFMU_ERR_ARG;
-  // apply in the fused kernel's epilogue when the workgroup owns whole rows: beta == 1 (closed-form denominators) on
-  // both kernels, beta != 1 (two accumulator sets) on the four-wave kernel in the single-plane precisions up to rank pad 128
-  const bool fuse = st->nsplit == 1 && st->owner.f && st->owner.p2_hi && st->owner.colsum && st->owner.colsum_part &&
-                    (kl || (NMFMU_FUSE_APPLY_TWO_ACC && st->precision != NMFMU_PREC_BF16X3 && st->r_pad <= 128));
-  int e = 0;
-  if (phase != 2) {  // the fused kernel (with nmf.py:78-92 in its epilogue when the workgroup owns whole rows)
-    e = fuse ? fused_dispatch(st, kModeMU, nullptr, st->owner.rows, st->panel.rows, S(stream), kl_den, true)
-             : nmfmu_mu_partial(st, stream);
-    if (e) return e;
-  }
-  if (phase != 1) {  // what is left: the column-sum finalize, or the whole apply
-    e = fuse ? launch_colsum_finalize(st->owner.colsum_part, st->owner.rows_pad / st->block_rows, st->r_pad,
-                                      st->owner.colsum, S(stream))
-             : nmfmu_mu_apply(st, nullptr, nullptr, 0, kl ? kl_den : nullptr, stream);
-  }
-  return e;
+  if (nmfmu_beta_kind(st->beta) == NMFMU_BETA_KL && !kl_den) return NMFMU_ERR_ARG;
+  return mu_step_common(st, kl_den, phase, nullptr, stream);
 }
 
 int nmfmu_colsum_nparts(const nmfmu_step* st) {
-  if (!st || (st->block_rows != 128 && st->block_rows != 256)) return NMFMU_ERR_ARG;
-  // fused apply (nsplit == 1): one partial per workgroup tile; otherwise one per apply-kernel stripe
-  return st->nsplit == 1 ? st->owner.rows_pad / st->block_rows : st->owner.rows_pad / apply_stripe_rows(st->owner.rows_pad);
+  if (!st || !valid_block_rows(st->block_rows)) return NMFMU_ERR_ARG;
+  // fused apply: one partial per workgroup tile; otherwise one per apply-kernel stripe
+  return owns_whole_rows(st, false) ? workgroups(st->owner.rows_pad, st->block_rows, 1) : st->owner.rows_pad / apply_stripe_rows(st->owner.rows_pad);
 }
 
 int nmfmu_pack_nparts(int rows_pad) { return rows_pad <= 0 ? NMFMU_ERR_ARG : rows_pad / apply_stripe_rows(rows_pad); }
@@ -419,16 +440,13 @@ static int apply_common(const nmfmu_step* st, const float* num, const float* den
   a.f16 = is_f16(st->precision);
   a.status = st->status;
   if (!a.p1_hi || !a.p2_hi || !a.colsum || !a.colsum_part) return NMFMU_ERR_ARG;
-  if (st->stage == NMFMU_STAGE_DMA_NOP2 && sp_eligible(st->r_pad, st->precision, st->beta)) a.p2_hi = a.p2_lo = nullptr;   // (see nmfmu.h)
-  if (st->stage == NMFMU_STAGE_DMA_LDSTR || st->stage == NMFMU_STAGE_DMA_SP128 || st->stage == NMFMU_STAGE_DMA_SP128_RB0) {
-    if (st->block_rows != 256 || !pp_ldstr_eligible(st->r_pad, st->precision, st->beta)) return NMFMU_ERR_UNSUPPORTED;
-    a.p2_hi = a.p2_lo = nullptr;
-  }
+  bool writes_p2 = true;
+  if (const int e = apply_image_rule(st, &writes_p2)) return e;
+  if (!writes_p2) a.p2_hi = a.p2_lo = nullptr;   // nobody reads the transposed images where the stage promises so
   return launch_apply(st->r_pad, a, st->precision == NMFMU_PREC_BF16X3, /*pack_only=*/false, S(stream));
 }
 
-int nmfmu_mu_apply(const nmfmu_step* st, const float* num, const float* den, int nslab, const float* kl_den,
-                   void* stream) {
+int nmfmu_mu_apply(const nmfmu_step* st, const float* num, const float* den, int nslab, const float* kl_den, void* stream) {
   return apply_common(st, num, den, nslab, kl_den, 0, 0.f, nullptr, stream);
 }
 
@@ -457,19 +475,14 @@ int nmfmu_xb_step(const nmfmu_step* st, const void* g_hi, const void* g_lo, cons
   // the workgroup owns whole rows (unsplit contraction): numerator, denominator (owner fragments x Gram image) and
   // nmf.py:78-92 in the kernel's epilogue; otherwise nsplit numerator slabs + ONE denominator slab (written by the first
   // min(nsplit, r_pad / 32) workgroups of every row block, one 32-rank tile each, the same MFMA product) + the apply kernel
-  const bool fuse = st->nsplit == 1 && st->owner.f && st->owner.p2_hi && st->owner.colsum && st->owner.colsum_part &&
-                    st->r_pad <= 128;
+  const bool fuse = owns_whole_rows(st, true) && st->r_pad <= 128;
   if (!fuse && !st->slab_den) return NMFMU_ERR_ARG;
-  const GramRef gm{nullptr, g_hi, g_lo, g_scale};
+  const GramRef gm{g_hi, g_lo, g_scale};
   int e = 0;
-  if (phase != 2) {
-    e = fused_dispatch(st, kModeXB, nullptr, st->owner.rows, st->panel.rows, S(stream), nullptr, fuse, &gm);
-    if (e) return e;
-  }
+  if (phase != 2) e = fused_dispatch(st, kModeXB, nullptr, st->owner.rows, st->panel.rows, S(stream), nullptr, fuse, &gm);
+  if (e || phase == 1 || fuse) return e;
   // (no column-sum finalize on this path: beta == 2 reads neither the closed-form denominators nor the fp16 scale)
-  if (phase != 1 && !fuse)
-    e = apply_common(st, nullptr, nullptr, 0, nullptr, 0, 0.f, nullptr, stream, /*den_nslab=*/1, /*skip_colsum=*/1);
-  return e;
+  return apply_common(st, nullptr, nullptr, 0, nullptr, 0, 0.f, nullptr, stream, /*den_nslab=*/1, /*skip_colsum=*/1);
 }
 
 int nmfmu_mu_step_allreduce(const nmfmu_step* st, nmfmu_comm* comm, float* xbuf, void* stream) {
@@ -492,13 +505,11 @@ int nmfmu_mu_step_allreduce(const nmfmu_step* st, nmfmu_comm* comm, float* xbuf,
   }
   e = nmfmu_comm_allreduce_sum_f32(comm, xbuf, plane + tail, stream);
   if (e) return e;
-  return kl ? nmfmu_mu_apply(st, xbuf, nullptr, 1, xbuf + plane, stream)
-            : nmfmu_mu_apply(st, xbuf, xbuf + plane, 1, nullptr, stream);
+  return nmfmu_mu_apply(st, xbuf, kl ? nullptr : xbuf + plane, 1, kl ? xbuf + plane : nullptr, stream);
 }
 
 int nmfmu_loss_part_count(int owner_rows_pad, int block_rows, int nsplit) {
-  if (block_rows != 128 && block_rows != 256) return NMFMU_ERR_ARG;
-  return (owner_rows_pad / block_rows) * nsplit;
+  return valid_block_rows(block_rows) ? workgroups(owner_rows_pad, block_rows, nsplit) : NMFMU_ERR_ARG;
 }
 
 int nmfmu_loss(const nmfmu_step* st, float* loss_part, double* out, void* stream) {
@@ -506,7 +517,7 @@ int nmfmu_loss(const nmfmu_step* st, float* loss_part, double* out, void* stream
   if (!nmfmu_supported(st->r_pad, st->precision)) return NMFMU_ERR_UNSUPPORTED;
   int e = fused_dispatch(st, kModeLoss, loss_part, st->owner.rows, st->panel.rows, S(stream));
   if (e) return e;
-  return launch_sum_finalize_f32(loss_part, (st->owner.rows_pad / st->block_rows) * st->nsplit, out, S(stream));
+  return launch_sum_finalize_f32(loss_part, workgroups(st->owner.rows_pad, st->block_rows, st->nsplit), out, S(stream));
 }
 
 int nmfmu_loss_checkpoint(const nmfmu_step* st, float* loss_part, double* out2, const float* fa, float* fa_snap, int64_t na,
@@ -515,19 +526,20 @@ int nmfmu_loss_checkpoint(const nmfmu_step* st, float* loss_part, double* out2, 
   if (!nmfmu_supported(st->r_pad, st->precision)) return NMFMU_ERR_UNSUPPORTED;
   int e = fused_dispatch(st, kModeLoss, loss_part, st->owner.rows, st->panel.rows, S(stream));
   if (e) return e;
-  return launch_checkpoint(loss_part, (st->owner.rows_pad / st->block_rows) * st->nsplit, st->status, out2, fa, fa_snap, na, fb,
+  return launch_checkpoint(loss_part, workgroups(st->owner.rows_pad, st->block_rows, st->nsplit), st->status, out2, fa, fa_snap, na, fb,
                            fb_snap, nb, S(stream));
 }
 
 int nmfmu_riding_loss_supported(const nmfmu_step* st) {
   // the half-steps whose kernel can carry the loss term: beta == 1 on the ping-pong kernel with fp16 operands (either target
   // width); unsplit contraction (fused apply) or split (partial sums + apply kernel) alike
-  if (!st || !st->xp || st->block_rows != 256 || !pp_eligible(st->r_pad, st->precision, st->beta) || !is_f16(st->precision)) return 0;
-  if (st->stage == NMFMU_STAGE_DMA_SPLIT || st->nsplit < 1 || !st->slab_num) return 0;
+  if (!st || !st->xp || !is_f16(st->precision)) return 0;
+  const Selection sel = select_kernel(st->r_pad, st->precision, st->beta, st->block_rows, st->stage, kModeMU, true);
+  if (sel.kernel != kPP || sel.err || st->stage == NMFMU_STAGE_DMA_SPLIT || st->nsplit < 1 || !st->slab_num) return 0;
   return st->owner.f && st->owner.colsum ? 1 : 0;
 }
 int nmfmu_riding_loss_part_count(const nmfmu_step* st) {
-  return nmfmu_riding_loss_supported(st) ? 16 * (st->owner.rows_pad / st->block_rows) * st->nsplit : NMFMU_ERR_UNSUPPORTED;
+  return nmfmu_riding_loss_supported(st) ? 16 * workgroups(st->owner.rows_pad, st->block_rows, st->nsplit) : NMFMU_ERR_UNSUPPORTED;
 }
 int nmfmu_target_sums_nparts(void) { return 1024; }
 int nmfmu_target_sums(const float* v, int64_t ld, int rows, int cols, double* part, double* out4, void* stream) {
@@ -538,13 +550,7 @@ int nmfmu_mu_step_with_loss(const nmfmu_step* st, const float* kl_den, float* xl
                             double* out2, void* stream) {
   if (!st || !kl_den || !xlogs_part || !target_sums || !out2) return NMFMU_ERR_ARG;
   if (!nmfmu_riding_loss_supported(st)) return NMFMU_ERR_UNSUPPORTED;
-  // (the same two launches as nmfmu_mu_step(st, kl_den, 0, stream), the first one on the kernel instance that also accumulates)
-  const bool fuse = st->nsplit == 1 && st->owner.p2_hi && st->owner.colsum_part;
-  int e = fuse ? fused_dispatch(st, kModeMU, xlogs_part, st->owner.rows, st->panel.rows, S(stream), kl_den, true)
-               : fused_dispatch(st, kModeMU, xlogs_part, st->owner.rows, st->panel.rows, S(stream));
-  if (e) return e;
-  e = fuse ? launch_colsum_finalize(st->owner.colsum_part, st->owner.rows_pad / st->block_rows, st->r_pad, st->owner.colsum, S(stream))
-           : nmfmu_mu_apply(st, nullptr, nullptr, 0, kl_den, stream);
+  const int e = mu_step_common(st, kl_den, 0, xlogs_part, stream);
   if (e) return e;
   return launch_riding_finish(xlogs_part, nmfmu_riding_loss_part_count(st) / 2, target_sums,
                               (double)st->owner.rows_pad * (double)st->panel.rows_pad, st->status, out2, S(stream));
@@ -692,15 +698,7 @@ int nmfmu_ubench_mfma_hbm2(const void* operands, size_t operand_bytes, int f16, 
   return rc == -2 ? NMFMU_ERR_UNSUPPORTED : rc;
 }
 
-int nmfmu_debug_set_buffer(void* buf) {
-#ifdef NMFMU_DEBUG_HOOKS
-  g_pp_debug = buf;
-  return NMFMU_OK;
-#else
-  (void)buf;
-  return NMFMU_ERR_UNSUPPORTED;   // diagnostic builds only
-#endif
-}
+int nmfmu_debug_set_buffer(void* buf) { return debug_set_buffer(buf); }   // (NMFMU_ERR_UNSUPPORTED outside diagnostic builds)
 
 int nmfmu_probe_mfma(const uint16_t* a, const uint16_t* b, float* d, void* stream) {
   if (!a || !b || !d) return NMFMU_ERR_ARG;

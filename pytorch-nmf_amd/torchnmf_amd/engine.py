@@ -49,19 +49,17 @@ class HipBackend:
         return bool(self.lib.nmfmu_supported(r_pad, precision))
 
     def block_rows(self, r_pad: int, precision: int, beta: float) -> int:
+        """Tile height of a half-step, either one (the two packed copies of the target are independent)."""
         return self.lib.nmfmu_block_rows(r_pad, precision, beta)
 
-    def step_block_rows(self, m_pad: int, k_pad: int, r_pad: int, precision: int, beta: float, device) -> int:
-        ncu = torch.cuda.get_device_properties(device).multi_processor_count
-        br = self.lib.nmfmu_step_block_rows(m_pad, k_pad, r_pad, precision, beta, ncu)
-        if br not in (128, 256):
-            _capi.check(br if br < 0 else _capi.ERR_ARG, 'nmfmu_step_block_rows')
-        return br
+    @staticmethod
+    def num_cu(device) -> int:
+        return torch.cuda.get_device_properties(device).multi_processor_count
 
     def choose_nsplit(self, m_pad: int, k_pad: int, block_rows: int, device, r_pad=None, precision=None, beta=None) -> int:
         """Contraction split of one half-step.  With (r_pad, precision, beta) the library sizes it for the kernel that will
         run (the software-pipelined rank-256 kernel holds ONE workgroup per CU, the four-wave kernel two)."""
-        ncu = torch.cuda.get_device_properties(device).multi_processor_count
+        ncu = self.num_cu(device)
         forced = os.environ.get('TORCHNMF_AMD_NSPLIT')        # experiment hook (tools/gpu_r6*.sh)
         if forced:
             return max(1, min(int(forced), k_pad // 64 // 4))
@@ -327,16 +325,62 @@ class StepRows:
     def nsplit_for(st: StepBuf, n: int, backend, k_pad: int, dev) -> int:
         """Its own contraction split: half the row blocks want twice the workgroups per block to fill the chip."""
         s0 = st.struct
-        try:
-            ns = backend.choose_nsplit(n, k_pad, st.block_rows, dev, s0.r_pad, s0.precision, s0.beta)
-        except TypeError:           # (the oracle-backed stand-in of the CPU tests: the plain rule)
-            ns = backend.choose_nsplit(n, k_pad, st.block_rows, dev)
-        return max(st.nsplit, ns)
+        return max(st.nsplit, choose_nsplit(backend, n, k_pad, st.block_rows, dev, s0.r_pad, s0.precision, s0.beta))
 
 
 # Factory of the compute backend.  It is HipBackend in the product; the CPU test-suite swaps in an oracle-backed
 # stand-in (tests/cpu_backend.py) to exercise the host logic (sharding, all-reduce packing, fit loop) without a GPU.
 DEFAULT_BACKEND_FACTORY = HipBackend
+
+
+def choose_nsplit(be, m_pad, k_pad, block_rows, dev, r_pad, precision, beta) -> int:
+    """Contraction split of a half-step, sized for the kernel it runs on where the backend can tell (the oracle-backed
+    stand-in of the CPU tests has the plain rule only)."""
+    try:
+        return be.choose_nsplit(m_pad, k_pad, block_rows, dev, r_pad, precision, beta)
+    except TypeError:
+        return be.choose_nsplit(m_pad, k_pad, block_rows, dev)
+
+
+def plan_tiles(be, sizes, r_pad, precision, beta, dev, block_rows=None):
+    """[(owner rows, panel rows, tile height, contraction split)] of the half-steps with the padded ``sizes`` [(owner rows,
+    panel rows)]: the library's tile height (or the forced one) and the split that goes with it."""
+    br = block_rows if block_rows is not None else be.block_rows(r_pad, precision, beta)
+    return [(m_pad, k_pad, br, choose_nsplit(be, m_pad, k_pad, br, dev, r_pad, precision, beta)) for m_pad, k_pad in sizes]
+
+
+def plan_stage(be, steps, r_pad, precision, beta, num_cu=None, sharded=False, update_W=True, block_rows=None, stage=None):
+    """The staging variant (``_capi.STAGE_*``) that every half-step of a DenseMU engine is built with.  ``steps``: the result of
+    ``plan_tiles``; ``num_cu``: the device's CU count, None off the GPU; ``block_rows`` / ``stage``: what the caller forced."""
+    if stage is not None:
+        return stage
+    # (round 6) beta == 1 at padded rank 256 with fp16 operands runs the software-pipelined kernel in BOTH half-steps and
+    # for the loss: ONE image per factor, GEMM2's operand gathered from it -- nothing reads the transposed images, so
+    # nobody has to keep them up to date (NMFMU_STAGE_DMA_NOP2: 17 % less epilogue traffic)
+    nop2 = (hasattr(be, 'kernel_family') and beta == 1.0 and r_pad == 256
+            and be.kernel_family(r_pad, precision, beta) == _capi.KERNEL_SP and os.environ.get('TORCHNMF_AMD_NO_P2', '1') != '0')
+    stage = _capi.STAGE_DMA_NOP2 if nop2 else _capi.STAGE_DMA
+    # beta == 1 at padded rank 128, unsharded, both factors updated: BOTH half-steps run the ping-pong MU kernel, whose
+    # NMFMU_STAGE_DMA_LDSTR instance fetches one panel image and builds the transposed tile in LDS -- nothing reads the
+    # factors' transposed images, nobody refreshes them.  (Sharded engines keep the two-image path; so does a forced
+    # 128-row tile, which runs the four-wave kernel.)
+    if not (not sharded and update_W and block_rows in (None, 256) and hasattr(be, 'pp_lds_transpose_supported')
+            and be.pp_lds_transpose_supported(r_pad, precision, beta) and be.block_rows(r_pad, precision, beta) == 256):
+        return stage
+    # 'f16' on the one-image path, both half-steps with at least one workgroup per CU: the software-pipelined four-wave form
+    # with 64 owner rows per wave (NMFMU_STAGE_DMA_SP128; bit-identical to the ping-pong kernel at equal splits, whole
+    # groups of four tiles per workgroup).  Launches that fill the chip run at the socket's power limit, which is where
+    # it was measured to pay (-3.6 % per iteration at configs[1], profiles/r08_sp128_ab.md); smaller launches were not
+    # measured and stay on the ping-pong kernel; so do contractions that do not split into whole groups of four tiles (the
+    # two kernels would round the split differently: no longer the same sums).  TORCHNMF_AMD_SP128=0 keeps the ping-pong
+    # kernel everywhere (A/B); TORCHNMF_AMD_SP128=rb0: the same kernel with its whole ratio stage in phase A (the other arm
+    # of the A/B of profiles/r09_sp128_respace_ab.md; bit-identical results)
+    sp128 = os.environ.get('TORCHNMF_AMD_SP128', '1')
+    if (precision == _capi.PREC_F16 and sp128 != '0' and num_cu is not None
+            and all(br == 256 and (m_pad // 256) * ns >= num_cu and (k_pad // 64) % (4 * ns) == 0
+                    for m_pad, k_pad, br, ns in steps)):
+        return _capi.STAGE_DMA_SP128_RB0 if sp128 == 'rb0' else _capi.STAGE_DMA_SP128
+    return _capi.STAGE_DMA_LDSTR
 
 
 def mu_gamma(beta: float) -> float:
@@ -485,7 +529,7 @@ class DenseMU(AsyncLossMixin):
         operand rounding down (both dimensions >= F16_MIN_DIM) and the data sit inside fp16's range.  On a sharded fit
         EVERY rank enters the same all-reduce, whatever its own shard looks like (shards of 4096, 4096, 4095
         columns must not disagree about entering a collective), and all take the weakest rank's answer."""
-        if (os.environ.get('TORCHNMF_AMD_AUTO_F16', '1') == '0' or not hasattr(_capi, 'PREC_F16')
+        if (os.environ.get('TORCHNMF_AMD_AUTO_F16', '1') == '0'
                 or not be.supported(r_pad, _capi.PREC_F16)):
             return None                                   # rank-invariant: same library, same environment on every rank
         dims_ok = min(V.shape) >= cls.F16_MIN_DIM
@@ -493,7 +537,7 @@ class DenseMU(AsyncLossMixin):
             return None
         in_range, exact = cls.f16_stats(V, W, H, be) if dims_ok else (False, False)
         level = 2 if (in_range and exact) else (1 if in_range else 0)      # 2: f16, 1: f16x, 0: neither
-        if level == 1 and not (hasattr(_capi, 'PREC_F16X') and be.supported(r_pad, _capi.PREC_F16X)
+        if level == 1 and not (be.supported(r_pad, _capi.PREC_F16X)
                                and os.environ.get('TORCHNMF_AMD_AUTO_F16X', '1') != '0'):
             level = 0
         if group is not None:
@@ -501,7 +545,7 @@ class DenseMU(AsyncLossMixin):
             flag = torch.tensor([level], dtype=torch.int32, device=V.device)
             dist.all_reduce(flag, op=dist.ReduceOp.MIN, group=group)
             level = int(flag.item())
-            if level == 1 and not (hasattr(_capi, 'PREC_F16X') and be.supported(r_pad, _capi.PREC_F16X)):
+            if level == 1 and not be.supported(r_pad, _capi.PREC_F16X):
                 level = 0
         return {2: 'f16', 1: 'f16x', 0: None}[level]
 
@@ -512,7 +556,7 @@ class DenseMU(AsyncLossMixin):
         nothing rounded that the parity bar can see -- except for beta == 2, where the target is an MFMA operand itself and stays fp32
         ('f16x').  Rank-invariant like its input (same library and environment on every rank)."""
         mode = cls.auto_single_plane(V, W, H, r_pad, be, group)
-        if (mode == 'f16x' and float(beta) != 2.0 and hasattr(_capi, 'PREC_F16R') and be.supported(r_pad, _capi.PREC_F16R)
+        if (mode == 'f16x' and float(beta) != 2.0 and be.supported(r_pad, _capi.PREC_F16R)
                 and os.environ.get('TORCHNMF_AMD_AUTO_F16R', '1') != '0'):
             mode = 'f16r'
         return mode
@@ -551,24 +595,16 @@ class DenseMU(AsyncLossMixin):
         self.precision = _capi.PRECISIONS[precision]
         if not self.be.supported(self.r_pad, self.precision):
             raise NotImplementedError(f'precision {precision!r} is not available for rank {R} (padded {self.r_pad})')
-        sp128_auto = False
-        if stage is None:
-            # (round 6) beta == 1 at padded rank 256 with fp16 operands runs the software-pipelined kernel in BOTH half-steps and
-            # for the loss: ONE image per factor, GEMM2's operand gathered from it -- nothing reads the transposed images, so
-            # nobody has to keep them up to date (NMFMU_STAGE_DMA_NOP2: 17 % less epilogue traffic)
-            nop2 = (hasattr(self.be, 'kernel_family') and hasattr(_capi, 'STAGE_DMA_NOP2') and float(beta) == 1.0
-                    and self.r_pad == 256 and self.be.kernel_family(self.r_pad, self.precision, float(beta)) == _capi.KERNEL_SP
-                    and os.environ.get('TORCHNMF_AMD_NO_P2', '1') != '0')
-            stage = _capi.STAGE_DMA_NOP2 if nop2 else _capi.STAGE_DMA
-            # beta == 1 at padded rank 128, unsharded, both factors updated: BOTH half-steps run the ping-pong MU kernel, whose
-            # NMFMU_STAGE_DMA_LDSTR instance fetches one panel image and builds the transposed tile in LDS -- nothing reads the
-            # factors' transposed images, nobody refreshes them.  (Sharded engines keep the two-image path; so does a forced
-            # 128-row tile, which runs the four-wave kernel.)
-            if (group is None and update_W and block_rows in (None, 256) and hasattr(self.be, 'pp_lds_transpose_supported')
-                    and self.be.pp_lds_transpose_supported(self.r_pad, self.precision, float(beta))
-                    and self.be.block_rows(self.r_pad, self.precision, float(beta)) == 256):
-                stage = _capi.STAGE_DMA_LDSTR
-                sp128_auto = self.precision == _capi.PREC_F16 and os.environ.get('TORCHNMF_AMD_SP128', '1') != '0'
+        # the plan, before any buffer exists: tile height and contraction split per half-step (H: owner axis N, contraction over
+        # C; W: the other way round), then the stage they are all built with
+        dev = V.device
+        n_pad, c_pad = self.be.pad_rows(N), self.be.pad_rows(Cc)
+        steps = plan_tiles(self.be, [(n_pad, c_pad)] + ([(c_pad, n_pad)] if update_W else []), self.r_pad, self.precision,
+                           self.beta, dev, block_rows)
+        # (the CU count as the backend's own split rule sees it; a backend without the query: the device's)
+        num_cu = getattr(self.be, 'num_cu', HipBackend.num_cu)(dev) if dev.type == 'cuda' else None
+        stage = plan_stage(self.be, steps, self.r_pad, self.precision, self.beta, num_cu, sharded=group is not None,
+                           update_W=update_W, block_rows=block_rows, stage=stage)
         # beta == 2 without the reconstruction (nmf.py:61-63 has no eps inside its grad_outputs): numerator = one streaming
         # GEMM over X, denominator through the panel's rank x rank Gram matrix -- a third of the MFMA work, HBM-bound.
         # fit()'s engines only (allow_gram): BetaMu reads numerator AND denominator slabs (p.grad = pos - neg).
@@ -576,7 +612,6 @@ class DenseMU(AsyncLossMixin):
                           and hasattr(self.be, 'xb_supported') and self.be.xb_supported(self.r_pad, self.precision, self.beta)
                           and os.environ.get('TORCHNMF_AMD_BETA2_GRAM', '1') != '0')
         gamma = mu_gamma(self.beta)
-        dev = V.device
 
         self.fW = FactorBuf(W, self.r_pad, self.precision, self.be)
         self.fH = FactorBuf(H, self.r_pad, self.precision, self.be)
@@ -584,46 +619,19 @@ class DenseMU(AsyncLossMixin):
         self.flags = torch.tensor([0, 0x7f800000], dtype=torch.int32, device=dev)
         # fp16 mode: bit 0 is set by any update that had to clamp a factor value at 65504 for its fp16 image
         self.status = torch.zeros(1, dtype=torch.int32, device=dev)
-        n_pad, c_pad = self.fH.rows_pad, self.fW.rows_pad
-        # tile height per half-step (the two packed copies of V are independent): the library's choice, or forced
-        def tile_rows(m_pad, k_pad):
-            if block_rows is not None:
-                return block_rows
-            if hasattr(self.be, 'step_block_rows'):
-                return self.be.step_block_rows(m_pad, k_pad, self.r_pad, self.precision, self.beta, dev)
-            return self.be.block_rows(self.r_pad, self.precision, self.beta)
-        br = tile_rows(n_pad, c_pad)
+        _, _, br, ns_h = steps[0]
         self.block_rows = br
-        # H half-step and loss: owner axis N, contraction over C
-        xp_h = self.be.pack_x(V, False, self.precision, br, n_pad, c_pad, self.flags)
-        ns_h = self._nsplit(n_pad, c_pad, br, dev)
         need_den = False if self.kl else ('one' if self.gram_path else True)   # no slab | one slab | nsplit slabs
+        # H half-step and loss
+        xp_h = self.be.pack_x(V, False, self.precision, br, n_pad, c_pad, self.flags)
         self.step_h = StepBuf(xp_h, self.fH, self.fW, R, self.r_pad, ns_h, self.precision, stage, br, self.beta, gamma,
                               l1, l2, need_den=need_den, status=self.status)
         self.step_w = None
         if update_W:
-            brw = tile_rows(c_pad, n_pad)
+            _, _, brw, ns_w = steps[1]
             xp_w = self.be.pack_x(V, True, self.precision, brw, c_pad, n_pad, None)
-            ns_w = self._nsplit(c_pad, n_pad, brw, dev)
             self.step_w = StepBuf(xp_w, self.fW, self.fH, R, self.r_pad, ns_w, self.precision, stage, brw, self.beta,
                                   gamma, l1, l2, need_den=need_den, status=self.status)
-        # 'f16' on the one-image path, both half-steps with at least one workgroup per CU: the software-pipelined four-wave form
-        # with 64 owner rows per wave (NMFMU_STAGE_DMA_SP128; bit-identical to the ping-pong kernel at equal splits, whole
-        # groups of four tiles per workgroup).  Launches that fill the chip run at the socket's power limit, which is where
-        # it was measured to pay (-3.6 % per iteration at configs[1], profiles/r08_sp128_ab.md); smaller launches were not
-        # measured and stay on the ping-pong kernel; so do contractions that do not split into whole groups of four tiles (the
-        # two kernels would round the split differently: no longer the same sums).  TORCHNMF_AMD_SP128=0 keeps the ping-pong
-        # kernel everywhere (A/B).
-        if sp128_auto and dev.type == 'cuda':
-            ncu = torch.cuda.get_device_properties(dev).multi_processor_count
-            steps = (self.step_h, self.step_w)
-            if all(st.block_rows == 256 and (st.owner.rows_pad // 256) * st.nsplit >= ncu
-                   and (st.panel.rows_pad // 64) % (4 * st.nsplit) == 0 for st in steps):
-                # TORCHNMF_AMD_SP128=rb0: the same kernel with its whole ratio stage in phase A (the other arm of the A/B of
-                # profiles/r09_sp128_respace_ab.md; bit-identical results)
-                rb0 = os.environ.get('TORCHNMF_AMD_SP128', '1') == 'rb0'
-                for st in steps:
-                    st.struct.stage = _capi.STAGE_DMA_SP128_RB0 if rb0 else _capi.STAGE_DMA_SP128
         self.gm = self.be.gram_alloc(self.r_pad, dev) if self.gram_path else None
         self.timer: Optional[KernelTimer] = None   # bench.py: times the fused launches live
         self.refresh_images()
@@ -701,14 +709,6 @@ class DenseMU(AsyncLossMixin):
         if self.step_w is not None:
             sw = self.step_w
             self.be.pack_x(V, True, self.precision, sw.block_rows, sw.owner.rows_pad, sw.panel.rows_pad, None, out=sw.xp)
-
-    def _nsplit(self, m_pad, k_pad, block_rows, dev):
-        """Contraction split of a half-step, sized for the kernel it runs on where the backend can tell (the oracle-backed
-        stand-in of the CPU tests has the plain rule only)."""
-        try:
-            return self.be.choose_nsplit(m_pad, k_pad, block_rows, dev, self.r_pad, self.precision, self.beta)
-        except TypeError:
-            return self.be.choose_nsplit(m_pad, k_pad, block_rows, dev)
 
     def refresh_images(self):
         """Re-derive bf16 images / column sums from the fp32 masters (after external edits of W / H)."""

@@ -722,3 +722,56 @@ def test_plca_rejects_f16x_with_a_clear_message():
     assert guard and {p.strip(" '") for p in guard.group(1).split(',')} == {'f16x', 'f16', 'f16r'}
     # the three fp16-operand modes are exactly the ones refused: every other precision name reaches the engine
     assert set(_capi.PRECISIONS) - {'f16x', 'f16', 'f16r'} == {'bf16', 'bf16x3'}
+
+
+# ---- DenseMU's launch plan: tile height, contraction split and stage, decided before any buffer exists ----------------
+class _LibQueries(engine.HipBackend):
+    """HipBackend's static queries on the real library for a device with ``ncu`` CUs; no GPU is touched."""
+
+    def __init__(self, ncu):
+        self.lib, self._ncu = _capi.load(), ncu
+
+    def num_cu(self, device):
+        return self._ncu
+
+
+# (N, C, rank, precision, beta, CUs, environment, flags of plan_stage) -> (tile height, split or None = any, stage) of BOTH
+# half-steps; the expected values were evaluated with the expressions DenseMU.__init__ held before the plan was a function
+_BIG = (4096, 4096, 128, 'f16', 1.0)
+_PLAN_CASES = {
+    'sp128': (_BIG + (256, {}, {}), (256, 16, _capi.STAGE_DMA_SP128)),
+    'sp128 off': (_BIG + (256, {'TORCHNMF_AMD_SP128': '0'}, {}), (256, 16, _capi.STAGE_DMA_LDSTR)),
+    'sp128 rb0': (_BIG + (256, {'TORCHNMF_AMD_SP128': 'rb0'}, {}), (256, 16, _capi.STAGE_DMA_SP128_RB0)),
+    '256 workgroups on 304 CUs': (_BIG + (304, {}, {}), (256, 16, _capi.STAGE_DMA_LDSTR)),
+    'bf16': ((4096, 4096, 128, 'bf16', 1.0, 256, {}, {}), (256, 16, _capi.STAGE_DMA_LDSTR)),
+    '512 x 512': ((512, 512, 128, 'f16', 1.0, 256, {}, {}), (256, 2, _capi.STAGE_DMA_LDSTR)),
+    'rank 64': ((600, 2000, 64, 'f16', 1.0, 256, {}, {}), (256, None, _capi.STAGE_DMA)),
+    'rank 100 beta 2': ((600, 2000, 100, 'f16', 2.0, 256, {}, {}), (128, None, _capi.STAGE_DMA)),
+    'rank 100 forced 128-row tiles': ((600, 2000, 100, 'f16', 1.0, 256, {}, {'block_rows': 128}), (128, None, _capi.STAGE_DMA)),
+    'rank 100 W frozen': ((600, 2000, 100, 'f16', 1.0, 256, {}, {'update_W': False}), (256, None, _capi.STAGE_DMA)),
+    'rank 100 sharded': ((600, 2000, 100, 'f16', 1.0, 256, {}, {'sharded': True}), (256, None, _capi.STAGE_DMA)),
+    'rank 200': ((600, 2000, 200, 'f16', 1.0, 256, {}, {}), (128, None, _capi.STAGE_DMA_NOP2)),
+    'rank 200 sharded': ((600, 2000, 200, 'f16', 1.0, 256, {}, {'sharded': True}), (128, None, _capi.STAGE_DMA_NOP2)),
+    'rank 200 NO_P2=0': ((600, 2000, 200, 'f16', 1.0, 256, {'TORCHNMF_AMD_NO_P2': '0'}, {}), (128, None, _capi.STAGE_DMA)),
+    'forced stage': (_BIG + (256, {}, {'stage': _capi.STAGE_DMA_SPLIT}), (256, 16, _capi.STAGE_DMA_SPLIT)),
+}
+
+
+@pytest.mark.parametrize('case', list(_PLAN_CASES))
+def test_dense_plan_tiles_split_and_stage(case, monkeypatch):
+    (N, Cc, rank, precision, beta, ncu, env, flags), (want_rows, want_split, want_stage) = _PLAN_CASES[case]
+    for name in ('TORCHNMF_AMD_SP128', 'TORCHNMF_AMD_NO_P2', 'TORCHNMF_AMD_NSPLIT'):
+        monkeypatch.delenv(name, raising=False)
+    for name, value in env.items():
+        monkeypatch.setenv(name, value)
+    be = _LibQueries(ncu)
+    r_pad, prec = be.pad_rank(rank), _capi.PRECISIONS[precision]
+    n_pad, c_pad = be.pad_rows(N), be.pad_rows(Cc)
+    sizes = [(n_pad, c_pad)] + ([(c_pad, n_pad)] if flags.get('update_W', True) else [])
+    steps = engine.plan_tiles(be, sizes, r_pad, prec, beta, None, flags.get('block_rows'))
+    assert [(m, k) for m, k, _, _ in steps] == sizes
+    for _, _, rows, split in steps:
+        assert rows == want_rows and (want_split is None or split == want_split), (steps, want_rows, want_split)
+    assert engine.plan_stage(be, steps, r_pad, prec, beta, ncu, **flags) == want_stage
+    assert engine.plan_stage(be, steps, r_pad, prec, beta, None, **flags) == (
+        _capi.STAGE_DMA_LDSTR if want_stage in (_capi.STAGE_DMA_SP128, _capi.STAGE_DMA_SP128_RB0) else want_stage)   # off the GPU
