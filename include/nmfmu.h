@@ -72,6 +72,8 @@ extern "C" {
                                   nmfmu_sp_ccd_sweep / nmfmu_sp_ccd_limit / nmfmu_sp_ccd_wg_waves / nmfmu_sp_ccd_lds_rows (NMF.fit(solver='ccd'):
                                   coordinate descent over the stored entries of a missing-data target, beta == 2; added at
                                   ABI 10, additive);
+                                  nmfmu_sp_wccd_sweep (NMF.fit(solver='ccd', unstored=omega): the same sweep with every
+                                  unstored entry a zero of confidence omega, 0 < omega < 1; added at ABI 10, additive);
                                10: nmfmu_plca_normalize / nmfmu_plca_z / nmfmu_plca3 take alpha as double (an argument changed its
                                   type: not additive).  The Dirichlet prior adds fp32(alpha - 1) with the subtraction in double,
                                   as the reference's in-place add does; fp32(alpha) - 1.f was off by 4.7e-5 relative at
@@ -946,6 +948,33 @@ int nmfmu_sp_ccd_lds_rows(int rank);   /* entries per row whose panel rows fit t
 int nmfmu_sp_ccd_sweep(const int32_t* rowptr, const int32_t* idx, const float* vals, const int32_t* order, int n_rows,
                        float* owner, const float* panel, int n_panel, int rank, float l1, float l2, float* scratch,
                        float* panel_t, int limit, int lds_rows, int wg_rows, void* stream);
+
+/* ---- weighted CCD: unstored entries are zeros of confidence omega, beta == 2 (additive entry; wccd.py)
+ * nmfmu_sp_wccd_sweep: one pass over the rank on owner [n_rows][rank], in place, for the objective
+ *   1/2 sum_stored (v - y)^2 + 1/2 omega sum_unstored y^2 + l1 sum f + l2/2 |f|^2,   0 < omega < 1,   y = <owner[i], panel[j]>.
+ * rowptr / idx / vals / order / scratch / limit / wg_rows as for nmfmu_sp_ccd_sweep; gram [rank][rank] = panel^T panel, SYMMETRIC
+ * as nmfmu_gram writes it (coordinate k reads its row k only).  With c = 1.0f - omega (fp32), every owner row i with stored
+ * entries e (panel row j_e, value v_e), on its own -- a row WITHOUT entries too (the Gram term acts on it; it is a one-wave row):
+ *   t_e = fma(-c, s_e, v_e),  s_e = sum_k owner[i][k] panel[j_e][k]    (k ascending, one fused multiply-add chain from 0)
+ *   for k = 0 .. rank-1:  d = sum_e panel[j_e][k]^2,  n = sum_e t_e panel[j_e][k],  q = sum_j owner[i][j] gram[k][j]
+ *                                                                  (j < k: the values this pass wrote, j >= k: the old ones)
+ *                         D  = fma(c, d, omega * gram[k][k])
+ *                         f' = max(eps, (fma(owner[i][k], D, fma(-omega, q, n)) - l1) / ((D + l2) + eps)),   eps = 2^-23
+ *                         t_e = fma(-(c * (f' - owner[i][k])), panel[j_e][k], t_e) for every e;   owner[i][k] = f'
+ * -- the exact minimiser of the objective along the coordinate, floored at eps.
+ * Arithmetic: fp32.  d and n: as in nmfmu_sp_ccd_sweep (per-lane chains over the lane's entries in ascending e, xor butterfly
+ * 32 .. 1 per wave, the waves' totals added in wave order).  q: lane l runs fma(owner[i][l + 64 m], gram[k][l + 64 m], q) for
+ * m = 0 .. 3 from 0 (coordinates beyond the rank left out), then the same butterfly; with 16 waves on a row every wave
+ * computes q itself, with identical bits.  panel[j_e][k] is gathered from the row-major panel.  The same operations in the
+ * same order wherever the residuals live: a row's bits depend on that row of owner, its entries, panel, gram, omega, l1, l2
+ * and wg_rows alone -- not on limit, order or the other rows.  Plain vector stores, no atomics: a repeated call is bitwise
+ * identical.  panel, gram, idx, vals are only read.
+ * Null rowptr / idx / vals / owner / panel / gram / scratch, owner == panel, n_rows < 0, n_panel <= 0, rank <= 0, limit outside
+ * 0 .. 512, wg_rows < 0, omega outside (0, 1) or not finite: NMFMU_ERR_ARG; rank > 256: NMFMU_ERR_UNSUPPORTED -- both before
+ * any device work. */
+int nmfmu_sp_wccd_sweep(const int32_t* rowptr, const int32_t* idx, const float* vals, const int32_t* order, int n_rows,
+                        float* owner, const float* panel, int n_panel, int rank, const float* gram, float omega, float l1,
+                        float l2, float* scratch, int limit, int wg_rows, void* stream);
 
 /* ---- shift-invariant PLCA (SIPLCA / SIPLCA2 / SIPLCA3, plca.py:376-606) on the NMFD GEMM path ----------------------
  * Same EM update as PLCA with W (C, R, *T), H (B, R, *Lh): factors are addressed [outer][rank][inner], the unscaled

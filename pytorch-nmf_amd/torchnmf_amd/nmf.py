@@ -19,6 +19,7 @@ on all four model classes; sparse-COO targets of ``sparse_fit`` are not implemen
 """
 from __future__ import annotations
 
+import numbers
 import os
 from collections.abc import Iterable
 from typing import Optional
@@ -419,6 +420,13 @@ class BaseComponent(nn.Module):
                          the stored set, O(nnz * rank) for every beta; beta <= 0 is admitted when the stored values are
                          strictly positive.  Exact fp32: ``precision`` is ignored and ``last_precision`` is 'fp32'.  A dense
                          target with a mask goes in as ``V.sparse_mask(mask)``.  NMF only, not sharded.
+                         A real number omega strictly between 0 and 1 (not a bool; 'zero' stands for 1, 'missing' for 0):
+                         implicit feedback -- stored entries carry weight 1 (stored zeros too: explicit negatives), every
+                         unstored entry is a zero observed with confidence omega (Hu, Koren, Volinsky 2008).  The loss is
+                         ``1/2 sum_stored (v - y)^2 + 1/2 omega sum_unstored y^2``, evaluated without the N x C product.
+                         beta == 2 with solver='ccd' only (``wccd.WeightedCcdEngine``), O(nnz R + (N + C) R^2) per
+                         iteration; a row or column without a stored entry goes to the floor.  NMF only, rank <= 256, not
+                         sharded, exact fp32.
           solver         'mu' (default): the multiplicative update.  'hals': cyclic coordinate descent (Cichocki & Phan 2009;
                          sklearn's default solver) for beta == 2 -- the same ``X @ panel`` and Gram matrix as a beta = 2 MU
                          half-step, then one Gauss-Seidel sweep over the rank per row (``hals.hals_sweep``): a few
@@ -438,13 +446,16 @@ class BaseComponent(nn.Module):
         """
         if solver not in ('mu', 'hals', 'ccd'):
             raise ValueError(f"solver must be 'mu', 'hals' or 'ccd', got {solver!r}")
+        # a real number (not a bool) for `unstored` is the confidence of the unstored zeros; its range is judged below, where
+        # the strings are
+        weight = float(unstored) if isinstance(unstored, numbers.Real) and not isinstance(unstored, bool) else None
         if solver == 'ccd':
             if float(beta) != 2.0:
                 raise NotImplementedError(f"solver='ccd': the coordinate minimiser is closed-form only for beta = 2, got "
                                           f"beta = {beta:g}")
             if not isinstance(self, NMF):
                 raise NotImplementedError(f"solver='ccd' is implemented for NMF only, not {type(self).__name__}")
-            if unstored != 'missing':
+            if weight is None and unstored != 'missing':
                 raise NotImplementedError("solver='ccd' fits the stored entries only and needs unstored='missing'; for a "
                                           "target whose unstored entries are observed zeros use solver='hals'")
             if process_group is not None:
@@ -464,14 +475,21 @@ class BaseComponent(nn.Module):
                 raise NotImplementedError("solver='hals' is not sharded (process_group must be None)")
             if self.W is not None and self.W.shape[1] > 256:
                 raise NotImplementedError(f"solver='hals': rank {self.W.shape[1]} > 256, the limit of the sparse kernels")
-        if unstored not in ('zero', 'missing'):
-            raise ValueError(f"unstored must be 'zero' or 'missing', got {unstored!r}")
+        if (unstored not in ('zero', 'missing')) if weight is None else not 0.0 < weight < 1.0:     # (a NaN fails too)
+            raise ValueError(f"unstored must be 'zero' or 'missing', or (solver='ccd') the weight of the unstored zeros, a "
+                             f"real number strictly between 0 and 1; got {unstored!r}")
+        if weight is not None and solver != 'ccd':
+            raise NotImplementedError(f"unstored={unstored!r}: confidence-weighted unstored zeros are fitted by "
+                                      f"solver='ccd' only (beta = 2), not by solver={solver!r}")
         if unstored == 'missing':
             if not V.is_sparse:
                 raise ValueError("unstored='missing' needs a sparse-COO target whose stored entries are the observed ones; "
                                  "for a dense V with a boolean mask pass V.sparse_mask(mask) (mask: a sparse-COO tensor)")
             if process_group is not None:
                 raise NotImplementedError("unstored='missing': sparse targets are not sharded")
+        if weight is not None and not V.is_sparse:
+            raise ValueError(f"unstored={unstored!r} needs a sparse-COO target: the weight is that of its unstored entries (a "
+                             f"dense target stores every entry)")
         sparse = V.is_sparse
         if sparse and not isinstance(self, NMF):
             raise NotImplementedError('sparse targets are supported by NMF only (as in the reference)')
@@ -505,10 +523,15 @@ class BaseComponent(nn.Module):
         if V.dtype != torch.float32:
             V = V.float()
         if solver == 'ccd':
-            from .ccd import CcdEngine
             if not (W.data.is_contiguous() and H.data.is_contiguous()):
                 W.data, H.data = W.data.contiguous(), H.data.contiguous()
-            eng = CcdEngine(V, W.data, H.data, l1, l2, update_W=W.requires_grad, update_H=H.requires_grad)
+            if weight is not None:
+                from .wccd import WeightedCcdEngine
+                eng = WeightedCcdEngine(V, W.data, H.data, weight, l1, l2, update_W=W.requires_grad,
+                                        update_H=H.requires_grad)
+            else:
+                from .ccd import CcdEngine
+                eng = CcdEngine(V, W.data, H.data, l1, l2, update_W=W.requires_grad, update_H=H.requires_grad)
         elif solver == 'hals':
             from .hals import HalsEngine
             if not (W.data.is_contiguous() and H.data.is_contiguous()):
