@@ -440,56 +440,16 @@ def fp32_order_error(lhs_planes, rhs, ref):
     return worst
 
 
-# ---- host mirror of ConvMU's path selection (nmfd_engine.py) -----------------------------------------------------------
-def _pad128(n):
-    return (n + 127) // 128 * 128
-
-
+# ---- ConvMU's path selection for a case -------------------------------------------------------------------------------
 def plan(case, ncu):
-    """The control flow ConvMU takes for a case on ``ncu`` CUs, from the host functions of nmfd_engine and the library's
-    documented predicates (nmfmu_fold_parts_supported: >= 128 taps and frames; nmfmu_conv_ragged_supported: the LDS budget;
-    nmfmu_gemm_ragged_supported: >= 1024 whole channels / frames).  The GPU test asserts the engine agrees."""
-    from torchnmf_amd import nmfd_engine as N
-    env = case['env']
-    on = lambda k: env.get('TORCHNMF_AMD_NMFD_' + k, '1') != '0'
-    B, C, R, ts, ls = case['B'], case['C'], case['R'], tuple(case['ts']), tuple(case['ls'])
-    lhs = tuple(l - t + 1 for l, t in zip(ls, ts))
-    nd = len(ts)
-    T, L, Lh = int(np.prod(ts)), int(np.prod(ls)), int(np.prod(lhs))
-    kl = float(case['beta']) == 1.0
-    cp, blp, rpp = _pad128(C), _pad128(B * L), _pad128(R * T)
-    slots = 2 * ncu
-    p = dict(T=T, L=L, Lh=Lh, c_pad=cp, bl_pad=blp, rp_pad=rpp)
-    p['implicit'] = ts[-1] % 8 == 0 and ls[-1] % 8 == 0 and env.get('TORCHNMF_AMD_NMFD_EXPLICIT', '0') != '1'
-    p['fold_parts'] = nd == 1 and T >= 128 and L >= 128 and on('FOLD_PARTS')
-    p['h_rows'] = T > 1 and not p['fold_parts'] and 2 * blp * cp < 2 ** 31 and on('H_ROWS')
-    c_main = C // 128 * 128
-    p['ragged'] = (nd == 1 and c_main >= 128 and 0 < C - c_main <= 8 and 8 * (2 * T + 63 + 8) * 4 <= 64 * 1024
-                   and on('RAGGED'))
-    p['ragged_in_grid'] = p['ragged'] and p['implicit'] and c_main >= 1024 and blp >= 1024 and on('RAGGED_IN_GRID')
-    p['c_rows'] = 64 if (nd > 1 and p['implicit'] and C <= 64 and on('NARROW')) else None
-    p['fused_sums'] = kl and p['fold_parts'] and on('FUSED_SUMS')
-    p['fused_tables'] = p['fused_sums'] and p['implicit'] and on('FUSED_TABLES')
-    p['h_tail'] = (0, 1)
-    want = env.get('TORCHNMF_AMD_NMFD_TAIL_SPLIT', '1')
-    if p['fold_parts'] and want != '0':
-        p['h_tail'] = N.tail_round_split(rpp // 128, blp // 128, slots, -(-C // 64), want)
-    p['wk_fold'] = p['h_ksplit'] = None
-    if p['h_rows']:
-        wk_rows = 32 if R <= 32 else 64 if R <= 64 else _pad128(R)
-        p['wk_fold'] = N.h_tap_fold(R, ts[-1]) if on('H_FOLD') else 1
-        wk_klen = (T // p['wk_fold']) * (-(-C // 64)) * 64
-        hj_pad = _pad128(B * (Lh // lhs[-1]) * (lhs[-1] + p['wk_fold'] - 1))
-        p['h_ksplit'] = N.w_contraction_split((hj_pad // 128) * -(-wk_rows // 128), wk_klen // 64, slots) if on('KSPLIT') else 1
-        p['wk_rows'], p['hj_pad'] = wk_rows, hj_pad
-    p['rows_fused'] = kl and p['h_rows'] and not p['fused_sums'] and T >= 64 and R <= 256 and on('ROWS_FUSED')
-    tiles = (cp // 128) * (rpp // 128)
-    kt_w = -(-(B * L) // 64) if (p['implicit'] and nd == 1) else blp // 64
-    p['w_ksplit'] = 1
-    if on('KSPLIT'):
-        p['w_ksplit'] = ((2 if (tiles <= 256 and kt_w % 2 == 0 and blp >= 2048) else 1) if p['fused_sums']
-                         else N.w_contraction_split(tiles, kt_w, slots))
-    return p
+    """The control flow ConvMU takes for a case on ``ncu`` CUs: nmfd_engine.plan_conv, the function the engine itself
+    plans with, on the case's sizes and switches alone (the library's static predicates run on the host), as a dict of the
+    plan's fields plus ``h_tail`` = (rows, split).  The GPU test asserts that the engine built for the case carries it."""
+    import dataclasses
+    from torchnmf_amd import _capi, nmfd_engine as N
+    p = dataclasses.asdict(N.plan_conv(_capi.load(), case['B'], case['C'], case['ls'], case['R'], case['ts'], case['beta'],
+                                       ncu=ncu, env=case['env']))
+    return dict(p, h_tail=(p['h_tail_rows'], p['h_tail_split']))
 
 
 def claim_holds(claim, p, case):
@@ -510,7 +470,7 @@ def claim_holds(claim, p, case):
     return bool(p[claim])
 
 
-# Claims only the library can answer (asserted on the GPU): staged[...] launches, nmfmu_fold_parts_supported, ragged support.
+# Claims only a launch can answer (asserted on the GPU): staged[...].
 def conv_cases():
     """The case list of tests/test_gpu_conv_emulated_parity.py.  Each case: shapes, precision, beta, environment switches,
     regularisation, the control-flow claims it is there for (checked against ``plan`` on the CPU and against the engine on

@@ -90,7 +90,8 @@ def _fault_problem(B=1, C=70, L=136, R=3, T=16, seed=5):
 def _judge(which, prec, beta, V, W, H, faulty, good, pad=None):
     """(per-element check passes, rel_err of the faulty factor against the unrounded oracle)."""
     C, BL = W.shape[0], V.shape[0] * V.shape[2]
-    rp, cp = (CE._pad128(C), CE._pad128(BL)) if which == 'w' else (CE._pad128(BL), CE._pad128(C))
+    p128 = lambda n: -(-n // 128) * 128
+    rp, cp = (p128(C), p128(BL)) if which == 'w' else (p128(BL), p128(C))
     got = CE.as_kernel_result(faulty, prec, which, rp, cp)
     if pad is not None:
         pad(got)

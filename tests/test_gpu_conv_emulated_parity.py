@@ -244,7 +244,7 @@ def test_conv_half_steps_per_element(dev, monkeypatch, case):
     else:
         eng = ConvMU(V.to(dev), W0.clone().to(dev), H0.clone().to(dev), beta, l1, l2, precision=prec)
     assert eng.precision_name == prec
-    # the case is what it says: the host mirror, then the engine itself
+    # the case is what it says: the plan from the sizes alone, then the engine itself
     flags = _flags(eng)
     p = CE.plan(case, _ncu())
     assert {k: p[k] for k in flags} == flags, (p, flags)

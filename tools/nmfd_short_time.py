@@ -30,7 +30,7 @@ for prec in os.environ.get('PRECISIONS', 'auto,bf16x3,bf16').split(','):
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / n
     out[prec] = {'precision': eng.precision_name, 'iters_per_s': round(1 / dt, 1), 'ms_per_iter': round(1e3 * dt, 4),
-                 'implicit': bool(eng.implicit), 'h_rows': bool(eng.h_rows), 'fold': getattr(eng, 'wk_fold', None),
+                 'implicit': bool(eng.implicit), 'h_rows': bool(eng.h_rows), 'fold': eng.wk_fold,
                  'w_ksplit': eng.w_ksplit, 'finite': bool(torch.isfinite(W).all() and torch.isfinite(H).all())}
     del eng
 print(json.dumps({'workload': f'NMFD 1x{Cc}x{L} rank {R} T={T} beta=1', 'modes': out}))

@@ -19,12 +19,12 @@ for rep in range(3):
     torch.cuda.synchronize(); print('ctor ok', eng.ragged, eng.fused_sums, eng.c_pad, eng.rp_pad, eng.bl_pad, flush=True)
     l0 = eng.divergence()
     torch.cuda.synchronize(); print('div ok', flush=True)
-    print('loss_part', eng.loss_part.shape, eng.loss_part.data_ptr() % 256, eng._loss_main, flush=True)
+    print('loss_part', eng.loss_part.shape, eng.loss_part.data_ptr() % 256, eng.loss_main, flush=True)
     c1 = eng.loss_part.clone(); torch.cuda.synchronize(); print('clone ok', flush=True)
     lp = c1.double(); torch.cuda.synchronize(); print('double ok', flush=True)
     lp = lp.cpu()
-    main = float(lp[:eng._loss_main].sum()); rag = lp[eng._loss_main:]
-    print(f'rep {rep}: l0={l0:.3f} main={main:.3f} (oracle {float(O.beta_div(rec[:, :128], V[:, :128], 1)):.3f}) ragged={float(rag.sum()):.3f} (oracle {float(O.beta_div(rec[:, 128:], V[:, 128:], 1)):.3f}) nrag={rag.numel()} stale tail={float(lp[eng._loss_main + 80:].abs().sum())}')
+    main = float(lp[:eng.loss_main].sum()); rag = lp[eng.loss_main:]
+    print(f'rep {rep}: l0={l0:.3f} main={main:.3f} (oracle {float(O.beta_div(rec[:, :128], V[:, :128], 1)):.3f}) ragged={float(rag.sum()):.3f} (oracle {float(O.beta_div(rec[:, 128:], V[:, 128:], 1)):.3f}) nrag={rag.numel()} stale tail={float(lp[eng.loss_main + 80:].abs().sum())}')
     per = rag[:80].view(8, 10).sum(1)
     want = torch.tensor([float(O.beta_div(rec[:, 128 + i:129 + i], V[:, 128 + i:129 + i], 1)) for i in range(8)])
     print('   per channel rel err', ((per - want) / want).tolist())
