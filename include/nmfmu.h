@@ -74,6 +74,9 @@ extern "C" {
                                   ABI 10, additive);
                                   nmfmu_sp_wccd_sweep (NMF.fit(solver='ccd', unstored=omega): the same sweep with every
                                   unstored entry a zero of confidence omega, 0 < omega < 1; added at ABI 10, additive);
+                                  nmfmu_fold_in_cd / nmfmu_fold_in_cd_block / nmfmu_fold_in_cd_long_rows (NMF.transform_cd(solver='ccd' |
+                                  'hals'): new rows folded in by coordinate descent, every iteration of a row in one launch;
+                                  added at ABI 10, additive);
                                10: nmfmu_plca_normalize / nmfmu_plca_z / nmfmu_plca3 take alpha as double (an argument changed its
                                   type: not additive).  The Dirichlet prior adds fp32(alpha - 1) with the subtraction in double,
                                   as the reference's in-place add does; fp32(alpha) - 1.f was off by 4.7e-5 relative at
@@ -895,6 +898,43 @@ int nmfmu_fold_in(const int32_t* rowptr, const int32_t* colidx, const float* val
                   int n_cols, int rank, float beta, int mode, const float* aux, float l1, float l2, float gamma,
                   int max_iter, float tol, int32_t* n_iter_rows, const int32_t* order, int block, int long_rows,
                   void* stream);
+
+/* ---- fold-in by coordinate descent, beta == 2 (additive entries; fold_in.py) --------------------------
+ * nmfmu_fold_in_cd: the new rows as for nmfmu_fold_in (CSR; H holds H0 on entry and the result on return; W read only), every
+ * iteration of every row in ONE launch, for the objective of a row h
+ *   1/2 sum_stored (v - y)^2 + 1/2 omega sum_unstored y^2 + l1 sum h + l2/2 |h|^2,   0 <= omega <= 1,   y_j = <h, W[j]>
+ * -- omega = 0: the stored entries only ('missing', nmfmu_sp_ccd_sweep's recurrence); 0 < omega < 1: nmfmu_sp_wccd_sweep's;
+ * omega = 1: every unstored entry an observed zero ('zero', HALS on the row).  gram [rank][rank] = W^T W, SYMMETRIC as nmfmu_gram
+ * writes it (coordinate k reads its row k only); may be NULL iff omega == 0.  With c = 1.0f - omega (fp32), per row, once:
+ *   d_k = sum_e W[j_e][k]^2,  D_k = fma(c, d_k, omega * gram[k][k])  (omega == 0: D_k = d_k),  omega == 1: n_k = sum_e v_e W[j_e][k]
+ * and max_iter times
+ *   t_e = fma(-c, s_e, v_e),  s_e = sum_k h[k] W[j_e][k]   (k ascending, one fused multiply-add chain from 0; formed anew from h
+ *                                                           in every iteration)
+ *   for k = 0 .. rank-1:  n = sum_e t_e W[j_e][k]  (omega == 1: n_k),   q = sum_j h[j] gram[k][j]   (omega == 0: none)
+ *                         h' = max(eps, (fma(h[k], D_k, fma(-omega, q, n)) - l1) / ((D_k + l2) + eps)),   eps = 2^-23
+ *                              (omega == 0: fma(h[k], D_k, n) - l1 above the same denominator)
+ *                         t_e = fma(-(c * (h' - h[k])), W[j_e][k], t_e) for every e;   h[k] = h'
+ * A row stops after iteration k when max_r |h_k[r] - h_{k-1}[r]| <= tol * max_r h_k[r] (fp32; tol == 0: never); n_iter_rows
+ * (may be NULL) receives the count.  A row without entries: omega == 0 leaves it untouched (count 1 with tol > 0, else max_iter),
+ * omega > 0 sweeps it.  There is no initial scaling: H is used as it comes.
+ * Arithmetic: fp32.  A row of at most long_rows entries (0 = nmfmu_fold_in_cd_long_rows(rank)) is worked by one wave, a longer
+ * one by the NW = 4 waves of its workgroup: wave w owns the entries [w per, (w + 1) per), per = ceil(count / NW), local entry i on
+ * lane i mod 64 as slot i / 64.  d, n, n_k: per-lane fused multiply-add chains over the slots in ascending order from 0, an xor
+ * butterfly 32 .. 1 per wave, the waves' totals added in wave order.  q: lane l runs fma(h[l + 64 m], gram[k][l + 64 m], q)
+ * for m = 0 .. 3 from 0 (coordinates beyond the rank left out), then the same butterfly.  block (0 = nmfmu_fold_in_cd_block(rank),
+ * also the largest value): the largest share per whose W rows are staged in LDS once per row; above it W[j_e][k] is gathered
+ * from W at every use -- the same floats.  A row whose share exceeds the wave's LDS (more than 7100 .. 9400 entries, by the rank) keeps no
+ * residuals and forms t_e from h as it stands for every coordinate.  order as for nmfmu_fold_in.  A row's bits depend on its
+ * entries, its row of H, W, gram, omega, l1, l2, max_iter, tol and long_rows alone -- not on block, order or the other rows;
+ * plain vector stores, no atomics: a repeated call is bitwise identical.
+ * Null rowptr / colidx / vals / H / W, H == W, gram NULL with omega > 0, rank <= 0, n_rows < 0, n_cols <= 0, max_iter < 0, tol < 0,
+ * block < 0, long_rows < 0, omega outside [0, 1] or not a number: NMFMU_ERR_ARG; rank > 256: NMFMU_ERR_UNSUPPORTED; n_rows == 0
+ * or max_iter == 0: NMFMU_OK without a launch, H untouched -- all before any device work. */
+int nmfmu_fold_in_cd_block(int rank);       /* the default (and largest) staged share of a rank; 0 outside 1 .. 256 */
+int nmfmu_fold_in_cd_long_rows(int rank);   /* the default count above which a row takes the workgroup: min(block, 128) */
+int nmfmu_fold_in_cd(const int32_t* rowptr, const int32_t* colidx, const float* vals, int n_rows, float* H, const float* W,
+                     int n_cols, int rank, const float* gram, float omega, float l1, float l2, int max_iter, float tol,
+                     int32_t* n_iter_rows, const int32_t* order, int block, int long_rows, void* stream);
 
 /* ---- HALS: coordinate descent for beta == 2 (additive entry; hals.py) ---------------------------------
  * nmfmu_hals_sweep: one Gauss-Seidel pass over the rank on f [rows][rank], in place, every row on its own.  With

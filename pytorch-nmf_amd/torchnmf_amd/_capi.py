@@ -187,6 +187,11 @@ SIGNATURES = {
     'nmfmu_fold_in': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                 C.c_float, C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float,
                                 C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    'nmfmu_fold_in_cd_block': (C.c_int, [C.c_int]),
+    'nmfmu_fold_in_cd_long_rows': (C.c_int, [C.c_int]),
+    'nmfmu_fold_in_cd': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                   C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
+                                   C.c_int, C.c_int, C.c_void_p]),
     'nmfmu_hals_sweep': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_float,
                                    C.c_void_p]),
     'nmfmu_sp_ccd_limit': (C.c_int, []),

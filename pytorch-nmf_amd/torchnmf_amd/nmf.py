@@ -693,6 +693,18 @@ class NMF(BaseComponent):
         return fold_in(self.W, V_new, beta, max_iter, tol, alpha, l1_ratio, unstored=unstored, H0=H0, generator=generator,
                        return_n_iter=return_n_iter)
 
+    def transform_cd(self, V_new, beta: float = 2, max_iter: int = 200, tol: float = 1e-4, alpha: float = 0,
+                     l1_ratio: float = 0, *, unstored='missing', solver: str = 'ccd', H0: Tensor = None, generator=None,
+                     return_n_iter: bool = False):
+        """``transform`` by coordinate descent for beta = 2 (``fold_in.fold_in_cd``): ``solver='ccd'`` with
+        ``unstored='missing'`` or the weight a ``fit(solver='ccd', unstored=omega)`` was trained with, ``solver='hals'`` with
+        ``unstored='zero'``; ``H0`` is used without an initial scaling.  The module is not modified and ``self.H`` plays no
+        part."""
+        from .fold_in import fold_in_cd
+        assert self.W is not None
+        return fold_in_cd(self.W, V_new, beta, max_iter, tol, alpha, l1_ratio, unstored=unstored, solver=solver, H0=H0,
+                          generator=generator, return_n_iter=return_n_iter)
+
     def _make_engine(self, V, beta, l1, l2, precision, group, allreduce=None):
         from .engine import DenseMU
         assert V.dim() == 2 and V.shape == (self.H.shape[0], self.W.shape[0]), \
