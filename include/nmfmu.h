@@ -77,6 +77,8 @@ extern "C" {
                                   nmfmu_fold_in_cd / nmfmu_fold_in_cd_block / nmfmu_fold_in_cd_long_rows (NMF.transform_cd(solver='ccd' |
                                   'hals'): new rows folded in by coordinate descent, every iteration of a row in one launch;
                                   added at ABI 10, additive);
+                                  nmfmu_rank_pairs / nmfmu_rank_pass / nmfmu_rank_ws (full-ranking evaluation: the rank of every
+                                  held-out pair among the admissible columns of its row; added at ABI 10, additive);
                                10: nmfmu_plca_normalize / nmfmu_plca_z / nmfmu_plca3 take alpha as double (an argument changed its
                                   type: not additive).  The Dirichlet prior adds fp32(alpha - 1) with the subtraction in double,
                                   as the reference's in-place add does; fp32(alpha) - 1.f was off by 4.7e-5 relative at
@@ -871,6 +873,36 @@ int64_t nmfmu_topk_ws(int n_rows, int k, int nsplit);
 int nmfmu_topk(const float* H, int N, const int32_t* row_ids, int n_rows, const float* W, int C, int rank, int k,
                const int32_t* ex_rowptr, const int32_t* ex_colidx, int nsplit, void* ws, float* out_val, int32_t* out_idx,
                void* stream);
+
+/* ---- full-ranking evaluation without the n_rows x C score matrix (additive entries; scoring.py) ---------
+ * Scores, the order and the exclusion pattern are nmfmu_topk's.  The held-out pattern is a CSR over the n_rows REQUESTED rows
+ * (row_ids, or rows 0 .. n_rows - 1 when it is NULL): ho_colidx[ho_rowptr[r] .. ho_rowptr[r + 1]), ascending, are the held-out
+ * columns of requested row r; n_pairs = ho_rowptr[n_rows] is read on the device.  ex_rowptr / ex_colidx are indexed by the
+ * original row, as in nmfmu_topk, and may be NULL.  For every pair e = (i, c):
+ *   out_score[e] = the score tile's fp32 value of (i, c), the bits nmfmu_topk returns for that row and column;
+ *   out_rank[e]  = the number of admissible columns j != c of row i with s_ij > s_ic, or s_ij == s_ic and j < c (0-based); -1
+ *                  when the exclusion pattern stores (i, c) itself;
+ *   out_admissible[r] = C - (stored columns of the row in the exclusion pattern).
+ * Three launches on `stream`: pass 0 extracts the scores and sets the -1 flags, pass 1 counts per (pair, split) into ws, pass 2
+ * adds the nsplit partial counts.  Counts are integers: the result does not depend on nsplit or on the form of the count.
+ *   nmfmu_rank_pairs : the three passes in order, every row choosing the form of its count (the per-lane scan above 24 held-out
+ *                      pairs, one ballot per threshold below).  A requested row with an empty held-out range writes nothing but
+ *                      its out_admissible; the entry does not learn n_pairs on the host, so a caller without pairs does not call.
+ *   nmfmu_rank_pass  : one of the passes alone (pass 0 / 1 / 2), for timing them apart; form 0 = as nmfmu_rank_pairs, 1 = the
+ *                      ballot form for every row, 2 = the scan form for every row, form > 2 = the scan form above `form`
+ *                      held-out pairs (pass 1 reads it; for measuring where the two forms cross).
+ *   nmfmu_rank_ws    : bytes of ws: n_pairs * nsplit * 4 (0 when an argument is < 1) -- a pure function of its arguments.
+ * Null pointers (row_ids and ex_rowptr may be NULL), sizes < 1, rank <= 0, nsplit < 1, a pass outside 0 .. 2, form < 0:
+ * NMFMU_ERR_ARG; rank > 256: NMFMU_ERR_UNSUPPORTED -- both before any device work.  No atomics: a repeated call is bitwise
+ * identical. */
+int64_t nmfmu_rank_ws(int64_t n_pairs, int n_rows, int nsplit);
+int nmfmu_rank_pairs(const float* H, int N, const int32_t* row_ids, int n_rows, const float* W, int C, int rank,
+                     const int32_t* ho_rowptr, const int32_t* ho_colidx, const int32_t* ex_rowptr, const int32_t* ex_colidx,
+                     int nsplit, void* ws, float* out_score, int32_t* out_rank, int32_t* out_admissible, void* stream);
+int nmfmu_rank_pass(int pass, int form, const float* H, int N, const int32_t* row_ids, int n_rows, const float* W, int C,
+                    int rank, const int32_t* ho_rowptr, const int32_t* ho_colidx, const int32_t* ex_rowptr,
+                    const int32_t* ex_colidx, int nsplit, void* ws, float* out_score, int32_t* out_rank,
+                    int32_t* out_admissible, void* stream);
 
 /* ---- fold-in: new rows against a fixed W, all iterations in one launch (additive entries; fold_in.py) ----
  * The new rows come as CSR (rowptr [n_rows + 1], colidx / vals [nnz], int32 indices below n_cols); H [n_rows][rank] holds the

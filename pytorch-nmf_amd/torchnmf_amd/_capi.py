@@ -183,6 +183,13 @@ SIGNATURES = {
     'nmfmu_topk_ws': (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     'nmfmu_topk': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                              C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'nmfmu_rank_ws': (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
+    'nmfmu_rank_pairs': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]),
+    'nmfmu_rank_pass': (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p]),
     'nmfmu_fold_in_block': (C.c_int, [C.c_int]),
     'nmfmu_fold_in': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                 C.c_float, C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float,

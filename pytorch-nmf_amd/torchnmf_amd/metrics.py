@@ -28,11 +28,11 @@ from torch import Tensor
 
 from . import _capi
 from .sparse_autograd import SparseTarget, sparse_beta_div
-from .scoring import score_pairs, topk_scores
+from .scoring import rank_scores, ranking_metrics, score_pairs, topk_scores
 from .fold_in import fold_in, fold_in_cd
 
 __all__ = ['kl_div', 'euclidean', 'is_div', 'beta_div', 'sparseness', 'SparseTarget', 'sparse_beta_div', 'score_pairs',
-           'topk_scores', 'fold_in', 'fold_in_cd']
+           'topk_scores', 'rank_scores', 'ranking_metrics', 'fold_in', 'fold_in_cd']
 
 
 def _beta_div_value(input: Tensor, target: Tensor, beta: float) -> Tensor:

@@ -681,6 +681,19 @@ class NMF(BaseComponent):
         from .scoring import topk_scores
         return topk_scores(self.H, self.W, k, rows=rows, exclude=exclude)
 
+    def rank_scores(self, heldout, exclude=None):
+        """``Ranks(rows, cols, ranks, scores, admissible)``: the rank of every stored position of ``heldout`` among all
+        columns of its row that ``exclude`` (typically the sparse training target) does not store, under ``topk``'s order
+        (``scoring.rank_scores`` on ``H``, ``W``; detached)."""
+        from .scoring import rank_scores
+        return rank_scores(self.H, self.W, heldout, exclude)
+
+    def ranking_metrics(self, heldout, ks=(10,), exclude=None):
+        """recall@k / precision@k / ndcg@k for every ``k`` in ``ks``, MRR, AUC and the number of evaluated rows, from the full
+        ranking of the held-out pairs (``scoring.ranking_metrics`` on ``H``, ``W``)."""
+        from .scoring import ranking_metrics
+        return ranking_metrics(self.H, self.W, heldout, ks, exclude)
+
     def transform(self, V_new, beta: float = 1, max_iter: int = 200, tol: float = 1e-4, alpha: float = 0,
                   l1_ratio: float = 0, *, unstored: str = 'zero', H0: Tensor = None, generator=None,
                   return_n_iter: bool = False):

@@ -503,6 +503,18 @@ class PLCA(BaseComponent):
         from .scoring import topk_scores
         return topk_scores(self.H.detach() * self.Z.detach(), self.W, k, rows=rows, exclude=exclude)
 
+    def rank_scores(self, heldout, exclude=None):
+        """``Ranks(rows, cols, ranks, scores, admissible)`` of the stored positions of ``heldout`` among the columns that
+        ``exclude`` does not store (``scoring.rank_scores`` on ``H * Z``, ``W``; detached)."""
+        from .scoring import rank_scores
+        return rank_scores(self.H.detach() * self.Z.detach(), self.W, heldout, exclude)
+
+    def ranking_metrics(self, heldout, ks=(10,), exclude=None):
+        """recall@k / precision@k / ndcg@k for every ``k`` in ``ks``, MRR, AUC and the number of evaluated rows
+        (``scoring.ranking_metrics`` on ``H * Z``, ``W``)."""
+        from .scoring import ranking_metrics
+        return ranking_metrics(self.H.detach() * self.Z.detach(), self.W, heldout, ks, exclude)
+
     def _make_em(self, Vn, precision):
         assert Vn.dim() == 2 and Vn.shape == (self.H.shape[0], self.W.shape[0])
         return _PlcaEM(Vn, self.W.data, self.H.data, self.Z.data, precision)

@@ -5,7 +5,12 @@
 ``topk_scores(H, W, k, rows, exclude)``      the ``k`` best admissible columns of every requested row -- recommendation,
                                              retrieval (``nmfmu_topk``: an exact-fp32 MFMA GEMM fused with the selection)
 
-Both read the fp32 factors ``H`` (N, R) and ``W`` (C, R) directly; nothing of size ``N x C`` or ``n_rows x C`` is allocated.
+``rank_scores(H, W, heldout, exclude)``      the rank of every held-out (row, column) pair among ALL admissible columns of
+                                             its row, under ``topk_scores``'s order (``nmfmu_rank_pairs``: the same score
+                                             tile, counted instead of selected)
+``ranking_metrics(H, W, heldout, ks, ...)``  recall@k / precision@k / ndcg@k for any k, MRR and AUC from those ranks
+
+All read the fp32 factors ``H`` (N, R) and ``W`` (C, R) directly; nothing of size ``N x C`` or ``n_rows x C`` is allocated.
 Outputs are detached: there is no autograd here (a held-out *loss* with gradients is ``sparse_beta_div(...,
 unstored='missing')`` on a test-set ``SparseTarget``).  Scores are taken to be finite: ``-inf`` marks an inadmissible
 column inside the kernel, so a score of ``-inf`` or NaN is never returned.
@@ -27,7 +32,10 @@ MAX_K = 128          # the partial kernel keeps ceil(k / 64) <= 2 list entries p
 TILE_ROWS = 64       # csrc/nmfmu_score.hip: kTopRows
 TILE_COLS = 128      # csrc/nmfmu_score.hip: kTopCols
 
+RANK_SCAN_ABOVE = 24  # csrc/nmfmu_rank.hip: kRkScanAbove -- rows with more held-out pairs count by the per-lane scan
+
 TopK = namedtuple('topk_scores', ['values', 'indices'])
+Ranks = namedtuple('rank_scores', ['rows', 'cols', 'ranks', 'scores', 'admissible'])
 
 
 def choose_nsplit(n_rows: int, C: int, n_cu: int) -> int:
@@ -198,3 +206,156 @@ def topk_scores(H: Tensor, W: Tensor, k: int, rows: Tensor = None, exclude=None,
                                nsplit, ws.data_ptr() if ws is not None else None, val.data_ptr(), idx.data_ptr(),
                                _stream()), 'nmfmu_topk')
     return TopK(val, idx.long())
+
+
+# ---- full ranking ------------------------------------------------------------------------------------------------------------
+def _check_ks(ks) -> tuple:
+    try:
+        ks = tuple(ks)
+    except TypeError:
+        raise ValueError(f'ks must be a sequence of ints >= 1, got {ks!r}') from None
+    for k in ks:
+        if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+            raise ValueError(f'ks must hold ints >= 1, got {k!r}')
+    return ks
+
+
+def _check_pattern(what: str, name: str, P, N: int, C: int) -> None:
+    if not (isinstance(P, SparseTarget) or (isinstance(P, Tensor) and P.is_sparse)):
+        raise ValueError(f'{what}: {name} must be a 2-D sparse COO tensor or a SparseTarget')
+    if tuple(P.shape) != (N, C):
+        raise ValueError(f'{what}: {name} {tuple(P.shape)} does not match (N, C) = {(N, C)}')
+
+
+def _check_rank_args(what: str, H, W, heldout, exclude) -> None:
+    _check_rank(H, W, what)
+    _check_factor_shapes(H, W, what)
+    _check_pattern(what, 'heldout', heldout, H.shape[0], W.shape[0])
+    if exclude is not None:
+        _check_pattern(what, 'exclude', exclude, H.shape[0], W.shape[0])
+    _check_factor_dtype(H, W, what)
+    _check_device(what, H, W, heldout, exclude)
+
+
+class _RankPlan:
+    """What one ``nmfmu_rank_pairs`` call reads and writes; ``args`` is its argument list (tools/bench_rank.py times the
+    passes apart through ``nmfmu_rank_pass(pass, form, *args)``).  ``args`` is None when there is no held-out pair."""
+
+    def __init__(self, H: Tensor, W: Tensor, heldout, exclude, nsplit=None, fill=None):
+        dev = H.device
+        N, C, R = H.shape[0], W.shape[0], H.shape[1]
+        h_rowptr, self.colidx = _exclude_csr(heldout, dev)
+        counts = torch.diff(h_rowptr)
+        self.n = n = self.colidx.numel()
+        self.rows = torch.repeat_interleave(torch.arange(N, device=dev), counts.long())      # coalesced order: row-major
+        self.ex = _exclude_csr(exclude, dev) if exclude is not None else None
+        self.admissible = torch.full((N,), C, dtype=torch.int64, device=dev)
+        if self.ex is not None:
+            self.admissible -= torch.diff(self.ex[0]).long()
+        self.scores = torch.empty(n, dtype=torch.float32, device=dev)
+        self.ranks = torch.empty(n, dtype=torch.int32, device=dev)
+        self.args = None
+        if n == 0:
+            return
+        self.row_ids = torch.nonzero(counts).flatten().to(torch.int32)      # the rows with held-out pairs (one host sync)
+        self.n_rows = n_rows = self.row_ids.numel()
+        # rows without a pair have equal consecutive pointers: the pointers of the kept rows are already the compact CSR
+        self.ho_rowptr = torch.cat([h_rowptr[self.row_ids.long()], h_rowptr[-1:]]).contiguous()
+        if nsplit is None:
+            nsplit = choose_nsplit(n_rows, C, torch.cuda.get_device_properties(dev).multi_processor_count)
+        self.nsplit = int(nsplit)
+        self.ws = torch.empty(_capi.load().nmfmu_rank_ws(n, n_rows, self.nsplit) // 4, dtype=torch.int32, device=dev)
+        self.adm_rows = torch.empty(n_rows, dtype=torch.int32, device=dev)
+        if fill is not None:
+            self.scores.fill_(fill)
+            self.ranks.fill_(-7)
+            self.adm_rows.fill_(-7)
+            self.ws.fill_(0x7f7f7f7f)
+        self.Hc, self.Wc = _f32(H), _f32(W)
+        rowptr, colidx = self.ex if self.ex is not None else (None, None)
+        # (an exclusion pattern without a stored entry: see topk_scores)
+        self.args = (self.Hc.data_ptr(), N, self.row_ids.data_ptr(), n_rows, self.Wc.data_ptr(), C, R,
+                     self.ho_rowptr.data_ptr(), self.colidx.data_ptr(),
+                     rowptr.data_ptr() if rowptr is not None else None,
+                     (colidx.data_ptr() if colidx.numel() else rowptr.data_ptr()) if colidx is not None else None,
+                     self.nsplit, self.ws.data_ptr(), self.scores.data_ptr(), self.ranks.data_ptr(), self.adm_rows.data_ptr())
+
+    def result(self) -> Ranks:
+        if self.args is not None:
+            self.admissible[self.row_ids.long()] = self.adm_rows.long()
+        return Ranks(self.rows, self.colidx.long(), self.ranks.long(), self.scores, self.admissible)
+
+
+def rank_scores(H: Tensor, W: Tensor, heldout, exclude=None, *, _nsplit=None, _fill=None, _form=None) -> Ranks:
+    """``Ranks(rows int64 [n], cols int64 [n], ranks int64 [n], scores fp32 [n], admissible int64 [N])``: for every stored
+    position ``(i, c)`` of ``heldout`` (a 2-D sparse-COO tensor (N, C) or a ``metrics.SparseTarget``; pattern only), in its
+    coalesced order, the number of admissible columns ``j != c`` of row ``i`` that come before ``c`` in ``topk_scores``'s total
+    order -- ``s_ij > s_ic``, or equal fp32 scores and ``j < c`` (0-based).  A column is admissible when ``exclude`` (same
+    types, pattern only, a stored zero counts) does not store it; the other held-out columns of the row compete like any
+    other column.  A pair that ``exclude`` also stores gets rank ``-1`` (its score is still returned).  ``admissible[i]`` is
+    the number of admissible columns of row ``i``, for every row.
+
+    ``scores`` are the bits ``topk_scores`` returns for that (row, column), so ``rank < k`` exactly when the column is among
+    ``topk_scores(H, W, k, exclude=exclude)``'s indices of the row.  Rank <= 256; factors are taken to be finite.  The result
+    is bitwise independent of how the columns are split over workgroups.  One host synchronisation (the rows with pairs).
+
+    ``_nsplit`` / ``_fill`` / ``_form`` are for the tests and the benchmark: force the number of column ranges; pre-fill
+    outputs and workspace; force the form of the count (1: one ballot per threshold, 2: the per-lane scan)."""
+    what = 'rank_scores'
+    _check_rank_args(what, H, W, heldout, exclude)
+    plan = _RankPlan(H, W, heldout, exclude, _nsplit, _fill)
+    if plan.args is not None:
+        lib = _capi.load()
+        if _form is None:
+            _capi.check(lib.nmfmu_rank_pairs(*plan.args, _stream()), 'nmfmu_rank_pairs')
+        else:
+            for p in range(3):
+                _capi.check(lib.nmfmu_rank_pass(p, int(_form), *plan.args, _stream()), 'nmfmu_rank_pass')
+    return plan.result()
+
+
+def metrics_from_ranks(r: Ranks, ks=(10,)) -> dict:
+    """The metrics of ``ranking_metrics`` from the output of ``rank_scores``: integer hit counts, float64 sums, torch ops on
+    ``[n]`` and ``[N]`` tensors."""
+    ks = _check_ks(ks)
+    dev, N = r.ranks.device, r.admissible.numel()
+    f64 = dict(dtype=torch.float64, device=dev)
+    valid = r.ranks >= 0
+    row, rk = r.rows[valid], r.ranks[valid]
+    t = torch.bincount(row, minlength=N)
+    use = t > 0
+    tu = t[use]
+    tf = tu.double()
+    out = {}
+    t_max = int(t.max()) if N else 0
+    for k in ks:
+        hit = rk < k
+        hits = torch.bincount(row[hit], minlength=N)[use]
+        out[f'recall@{k}'] = (hits.double() / tf).mean()
+        out[f'precision@{k}'] = (hits.double() / k).mean()
+        dcg = torch.zeros(N, **f64).index_add_(0, row[hit], 1.0 / torch.log2(rk[hit].double() + 2.0))[use]
+        # ideal[p] = sum_{q < p} 1 / log2(q + 2): the row's min(k, t) pairs at the top
+        m = min(k, t_max)
+        ideal = torch.cat([torch.zeros(1, **f64), torch.cumsum(1.0 / torch.log2(torch.arange(m, **f64) + 2.0), 0)])
+        out[f'ndcg@{k}'] = (dcg / ideal[tu.clamp(max=k)]).mean()
+    best = torch.full((N,), 2 ** 62, dtype=torch.int64, device=dev).scatter_reduce_(0, row, rk, 'amin')[use]
+    out['mrr'] = (1.0 / (1.0 + best.double())).mean()
+    neg = (r.admissible[use] - tu)
+    above = torch.zeros(N, dtype=torch.int64, device=dev).index_add_(0, row, rk)[use] - tu * (tu - 1) // 2
+    ok = neg > 0
+    out['auc'] = (1.0 - above[ok].double() / (tf[ok] * neg[ok].double())).mean()
+    out['rows'] = use.sum().double()
+    return out
+
+
+def ranking_metrics(H: Tensor, W: Tensor, heldout, ks=(10,), exclude=None) -> dict:
+    """Full-ranking metrics of the held-out pairs as 0-dim float64 device tensors: ``'recall@k'``, ``'precision@k'``,
+    ``'ndcg@k'`` for every ``k`` in ``ks`` (any int >= 1, not limited to ``MAX_K``), ``'mrr'``, ``'auc'`` and ``'rows'``.  They
+    are means over the rows with at least one valid held-out pair (rank >= 0), ``'rows'`` is the number of such rows.  Per
+    row, with ``t`` valid pairs of ranks ``r_e``: recall@k = #{r_e < k} / t; precision@k = #{r_e < k} / k; ndcg@k =
+    sum_{r_e < k} 1 / log2(r_e + 2) over sum_{p < min(k, t)} 1 / log2(p + 2); mrr = 1 / (1 + min r_e); auc = 1 - (sum r_e -
+    t (t - 1) / 2) / (t (admissible - t)), a row with admissible == t left out of the AUC mean.  Without such rows a mean
+    is NaN."""
+    ks = _check_ks(ks)
+    _check_rank_args('ranking_metrics', H, W, heldout, exclude)
+    return metrics_from_ranks(rank_scores(H, W, heldout, exclude), ks)
