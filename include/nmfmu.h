@@ -79,6 +79,9 @@ extern "C" {
                                   added at ABI 10, additive);
                                   nmfmu_rank_pairs / nmfmu_rank_pass / nmfmu_rank_ws (full-ranking evaluation: the rank of every
                                   held-out pair among the admissible columns of its row; added at ABI 10, additive);
+                                  nmfmu_wmu_terms / nmfmu_wmu_step / nmfmu_wmu_loss / nmfmu_wmu_ws / nmfmu_wmu_nsplit /
+                                  nmfmu_wmu_loss_parts (NMF.fit(V, weights=M): dense per-entry weights or a dense mask on one
+                                  fused exact-fp32 MFMA kernel; added at ABI 10, additive);
                                10: nmfmu_plca_normalize / nmfmu_plca_z / nmfmu_plca3 take alpha as double (an argument changed its
                                   type: not additive).  The Dirichlet prior adds fp32(alpha - 1) with the subtraction in double,
                                   as the reference's in-place add does; fp32(alpha) - 1.f was off by 4.7e-5 relative at
@@ -807,6 +810,43 @@ int nmfmu_sp_masked_step(const int32_t* seg, int n_seg, const int32_t* multi, in
                          float gamma, float* ws, int r_pad, void* stream);
 int nmfmu_sp_masked_loss(const int32_t* seg, int n_seg, const int32_t* colidx, const float* vals, const float* owner,
                          const float* panel, int rank, float beta, double v_term, double* part, double* out, void* stream);
+
+/* ---- weighted NMF on a dense target: dense per-entry weights or a dense mask, every beta (additive entries) -------------------
+ * L = sum_ij m_ij d_beta(v_ij | y_ij), y = H W^T, m >= 0.  V and M are row-major [n][c] fp32 with the row stride ld (floats).
+ * side 0 is the H half (owner = H [n][rank], panel = W [c][rank], contraction over the columns of V), side 1 the W half
+ * (owner = W, panel = H, V and M walked along their columns in place: no transposed copy exists).  Both seeds of nmf.py:61-74
+ * are multiplied by m:
+ *   num[i][r] = sum_k (m g_neg(v, y))(i, k) panel[k][r],   den[i][r] = sum_k (m g_pos(y))(i, k) panel[k][r]
+ * (g_neg / g_pos as listed for the missing-data entries above).  Where m == 0 the entry is selected away, not multiplied:
+ * V may hold NaN, Inf or a negative value there.  One fused exact-fp32 MFMA kernel (v_mfma_f32_32x32x2_f32: y over the full
+ * padded rank, the elementwise seeds in LDS, both accumulators in registers; y and m g never reach HBM).  The contraction
+ * is cut into parts of whole 32-step stages: nsplit == 0 takes nmfmu_wmu_nsplit(owner rows, contraction, r_pad), a pure
+ * function of the shape; nsplit > 0 asks for that many (no empty part, only the last one short).  The parts' planes go to
+ * ws [part][num | den][owner rows][r_pad] with plain stores and a second kernel adds them in part order: no atomics, no
+ * fences -- a repeated call is bitwise identical whatever ws held.  16-byte loads of V and M when ld % 4 == 0 and both bases
+ * are 16-byte aligned, scalar loads otherwise.
+ *   nmfmu_wmu_ws         : floats of `ws` = parts * 2 * rows * r_pad -- a pure function of its four arguments (0 if one is bad)
+ *   nmfmu_wmu_terms      : num, den [owner rows][r_pad]; every element is written, the padded columns with 0.  den - num is
+ *                          the gradient of the weighted loss with respect to the owner.
+ *   nmfmu_wmu_step       : the same terms, then nmf.py:78-92 in place on the owner's fp32 master [owner rows][rank]:
+ *                          f *= ((relu(num) + eps) / (relu(den) + eps + l1 + l2 f))^gamma, applied by the second kernel once
+ *                          every part of every row tile is done (each reads the owner).  owner != panel.
+ *   nmfmu_wmu_loss       : *out = sum_ij m_ij (the term of metrics.beta_div at (i, j)), the reference's eps conventions per
+ *                          branch (metrics.py:22, 39, 57, 85-96).  The terms that hold y are summed in double per lane, per
+ *                          wave, per workgroup, then in block order; v_term carries sum m (the terms of v alone), formed by
+ *                          the caller in float64 as for nmfmu_sp_masked_loss.  part: nmfmu_wmu_loss_parts(n, c) doubles.
+ * Null pointers, n, c, rank <= 0, ld < c, side not 0 / 1, r_pad != nmfmu_pad_rank(rank), nsplit < 0: NMFMU_ERR_ARG; rank > 256:
+ * NMFMU_ERR_UNSUPPORTED -- both before any device work. */
+int nmfmu_wmu_nsplit(int rows, int contraction, int r_pad);
+int64_t nmfmu_wmu_ws(int rows, int contraction, int r_pad, int nsplit);
+int nmfmu_wmu_terms(const float* V, const float* M, int64_t ld, int n, int c, int side, const float* owner,
+                    const float* panel, int rank, int r_pad, float beta, int nsplit, float* ws, float* num, float* den,
+                    void* stream);
+int nmfmu_wmu_step(const float* V, const float* M, int64_t ld, int n, int c, int side, float* owner, const float* panel,
+                   int rank, int r_pad, float beta, float l1, float l2, float gamma, int nsplit, float* ws, void* stream);
+int nmfmu_wmu_loss_parts(int n, int c);
+int nmfmu_wmu_loss(const float* V, const float* M, int64_t ld, int n, int c, const float* H, const float* W, int rank,
+                   float beta, double v_term, double* part, double* out, void* stream);
 
 /* ---- PLCA's EM update (plca.py:248-290) -----------------------------------------------------------------------------
  * With G = Vn / (H diag(Z) W^T + eps) the factor "gradients" are (G^T H) * Z, (G W) * Z and Z.grad[r] = sum W * (G^T H);

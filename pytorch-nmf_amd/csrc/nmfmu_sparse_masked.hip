@@ -22,41 +22,10 @@
 
 #include "../../include/nmfmu.h"
 #include "nmfmu_fused.h"
+#include "nmfmu_mu_terms.h"
 #include "nmfmu_sparse_common.h"
 
 namespace nmfmu {
-
-// (g_neg, g_pos) of one stored entry; s is the plain dot product
-template <int KIND>
-__device__ __forceinline__ void masked_g(float v, float s, float beta, float& gn, float& gp) {
-  if constexpr (KIND == NMFMU_BETA_EUC) {
-    gn = v, gp = s;                                   // nmf.py:62-63
-  } else if constexpr (KIND == NMFMU_BETA_KL) {
-    gn = v / (s + kEps), gp = 1.f;                    // nmf.py:65; the ones seed
-  } else if constexpr (KIND == NMFMU_BETA_IS) {
-    const float r = 1.f / (s + kEps);                 // nmf.py:68-70
-    gp = r, gn = r * r * v;
-  } else {
-    const float se = s + kEps;                        // nmf.py:72-74
-    const float p2 = exp2f((beta - 2.f) * log2f(se));
-    gn = p2 * v, gp = p2 * se;
-  }
-}
-
-struct MaskedApply {
-  float l1, l2, gamma;
-};
-
-// nmf.py:78-92 on one element
-__device__ __forceinline__ float masked_apply(float f, float num, float den, const MaskedApply& ap) {
-  const float neg = fmaxf(num, 0.f) + kEps;
-  float pos = fmaxf(den, 0.f) + kEps;
-  if (ap.l1 > 0.f) pos += ap.l1;
-  if (ap.l2 > 0.f) pos += ap.l2 * f;
-  float mult = neg / pos;
-  if (ap.gamma != 1.f) mult = powf(mult, ap.gamma);
-  return f * mult;
-}
 
 // the shared epilogue of a finished row: r < r_pad, f = owner[row][r] (step only)
 __device__ __forceinline__ void masked_finish(int step, float* owner, float* __restrict__ num, float* __restrict__ den,
@@ -142,25 +111,6 @@ __global__ void __launch_bounds__(256) sp_masked_finish_kernel(const int32_t* __
     sum_partials<2>(nd, ws, mu, r, r_pad);
     const float f = (step && r < rank) ? owner[(size_t)mu.row * rank + r] : 0.f;
     masked_finish(step, owner, num, den, mu.row, r, rank, r_pad, f, nd[0], nd[1], ap);
-  }
-}
-
-// the s-dependent term of metrics.beta_div at one stored entry, in double (see nmfmu_sp_masked_loss in include/nmfmu.h)
-template <int KIND>
-__device__ __forceinline__ double masked_loss_term(float v, float s, float beta) {
-  if constexpr (KIND == NMFMU_BETA_EUC) {
-    const float d = s - v;                            // metrics.py:39
-    return (double)d * (double)d;
-  } else if constexpr (KIND == NMFMU_BETA_KL) {
-    return (double)s - (double)(v * logf(s + kEps));  // metrics.py:22
-  } else if constexpr (KIND == NMFMU_BETA_IS) {
-    const float se = s + kEps;                        // metrics.py:56-57
-    return (double)((v + kEps) / se) + (double)logf(se);
-  } else {
-    const float se = s + kEps;                        // metrics.py:85-95
-    const float vt = beta < 0.f ? v + kEps : v;
-    const float pb1 = exp2f((beta - 1.f) * log2f(se));
-    return (double)pb1 * ((double)(beta - 1.f) * (double)se - (double)beta * (double)vt);
   }
 }
 

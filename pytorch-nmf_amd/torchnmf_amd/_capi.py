@@ -174,6 +174,15 @@ SIGNATURES = {
                                        C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_void_p]),
     'nmfmu_sp_masked_loss': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float,
                                        C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'nmfmu_wmu_nsplit': (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    'nmfmu_wmu_ws': (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    'nmfmu_wmu_terms': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                  C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'nmfmu_wmu_step': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                 C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
+    'nmfmu_wmu_loss_parts': (C.c_int, [C.c_int, C.c_int]),
+    'nmfmu_wmu_loss': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float,
+                                 C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     'nmfmu_sp_plca_estep': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     'nmfmu_sp_plca_gather': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -20,6 +20,10 @@ reference's ``beta_div`` over the stored entries alone, for any beta
 ``score_pairs`` / ``topk_scores`` (``scoring.py``) use a fitted model without the ``N x C`` product: its value at
 (row, column) pairs, and the ``k`` best admissible columns per row.  ``fold_in`` (``fold_in.py``) gives ``H`` for rows that
 were not in the training target, with ``W`` fixed.
+
+``weighted_beta_div(H, W, V, weights, beta)`` (``wmu.py``) is the divergence between ``H @ W.T`` and a DENSE target with dense
+per-entry weights (a mask, exposures, confidences), for any beta, without the ``N x C`` product and differentiable with respect
+to both factors (``nmfmu_wmu_loss`` / ``nmfmu_wmu_terms``): the loss ``NMF.fit(V, weights=...)`` minimises.
 """
 from __future__ import annotations
 
@@ -30,9 +34,10 @@ from . import _capi
 from .sparse_autograd import SparseTarget, sparse_beta_div
 from .scoring import rank_scores, ranking_metrics, score_pairs, topk_scores
 from .fold_in import fold_in, fold_in_cd
+from .wmu import WeightedTarget, weighted_beta_div
 
 __all__ = ['kl_div', 'euclidean', 'is_div', 'beta_div', 'sparseness', 'SparseTarget', 'sparse_beta_div', 'score_pairs',
-           'topk_scores', 'rank_scores', 'ranking_metrics', 'fold_in', 'fold_in_cd']
+           'topk_scores', 'rank_scores', 'ranking_metrics', 'fold_in', 'fold_in_cd', 'WeightedTarget', 'weighted_beta_div']
 
 
 def _beta_div_value(input: Tensor, target: Tensor, beta: float) -> Tensor:

@@ -381,7 +381,8 @@ class BaseComponent(nn.Module):
     @torch.no_grad()
     def fit(self, V: Tensor, beta: float = 1, tol: float = 1e-4, max_iter: int = 200, verbose: bool = False,
             alpha: float = 0, l1_ratio: float = 0, *, precision: Optional[str] = None, process_group=None,
-            allreduce: Optional[str] = None, unstored: str = 'zero', solver: str = 'mu') -> int:
+            allreduce: Optional[str] = None, unstored: str = 'zero', weights: Optional[Tensor] = None,
+            solver: str = 'mu') -> int:
         """Minimise the beta-divergence between ``V`` and the model by multiplicative updates.
 
         Same contract as the reference (nmf.py:297-409): W half-step, then H
@@ -427,6 +428,19 @@ class BaseComponent(nn.Module):
                          beta == 2 with solver='ccd' only (``wccd.WeightedCcdEngine``), O(nnz R + (N + C) R^2) per
                          iteration; a row or column without a stored entry goes to the floor.  NMF only, rank <= 256, not
                          sharded, exact fp32.
+          weights        dense targets only: a tensor of V's shape on V's device -- a mask (bool), counts or exposures
+                         (integer) or per-entry confidences such as inverse noise variances (floating), every value finite
+                         and >= 0; converted to fp32 once.  The fit minimises ``sum_ij weights_ij * d_beta(V_ij | (H W^T)_ij)``:
+                         both seeds of the multiplicative update are multiplied by the weight and the tracked loss is
+                         ``metrics.weighted_beta_div``.  An entry of weight 0 counts for nothing WHATEVER V holds there (NaN,
+                         Inf, a negative value: mark missing data with NaN); beta <= 0 is admitted when V is strictly
+                         positive wherever the weight is.  One fused exact-fp32 MFMA kernel per half-step
+                         (``wmu.WeightedMU``), 12 N C rank flop per iteration whatever the weights: ``precision`` is ignored
+                         and ``last_precision`` is 'fp32'.  A mask that keeps a small part of V is cheaper as
+                         ``fit(V.sparse_mask(mask), unstored='missing')``, whose cost follows the stored entries: measured at
+                         4096 x 65536 the weighted kernel is faster once the mask keeps more than about
+                         5 % of V at rank 64 and 13 % at rank 128 (3.9x - 9.9x at a density of 0.5).  None (default): the
+                         unweighted fit, bit for bit.  NMF only, solver='mu', rank <= 256, not sharded.
           solver         'mu' (default): the multiplicative update.  'hals': cyclic coordinate descent (Cichocki & Phan 2009;
                          sklearn's default solver) for beta == 2 -- the same ``X @ panel`` and Gram matrix as a beta = 2 MU
                          half-step, then one Gauss-Seidel sweep over the rank per row (``hals.hals_sweep``): a few
@@ -449,6 +463,21 @@ class BaseComponent(nn.Module):
         # a real number (not a bool) for `unstored` is the confidence of the unstored zeros; its range is judged below, where
         # the strings are
         weight = float(unstored) if isinstance(unstored, numbers.Real) and not isinstance(unstored, bool) else None
+        if weights is not None:
+            # judged before anything else touches the target or the device; the scan of the values comes last
+            if V.is_sparse:
+                raise NotImplementedError("weights: a sparse target is not weighted per entry; its stored set is the mask -- "
+                                          "fit(V, unstored='missing') fits the stored entries only")
+            if not isinstance(self, NMF):
+                raise NotImplementedError(f'weights are implemented for NMF only, not {type(self).__name__}')
+            if process_group is not None:
+                raise NotImplementedError('weights: a weighted fit is not sharded (process_group must be None)')
+            if solver != 'mu':
+                raise NotImplementedError(f"weights are fitted by solver='mu' only, not by solver={solver!r}")
+            if self.W is not None and self.W.shape[1] > 256:
+                raise NotImplementedError(f'weights: rank {self.W.shape[1]} > 256, the limit of the exact-fp32 kernels')
+            from .wmu import check_weights
+            weights = check_weights(V, weights)
         if solver == 'ccd':
             if float(beta) != 2.0:
                 raise NotImplementedError(f"solver='ccd': the coordinate minimiser is closed-form only for beta = 2, got "
@@ -508,7 +537,8 @@ class BaseComponent(nn.Module):
             W.data, H.data = W.data.float().contiguous(), H.data.float().contiguous()
             try:
                 return self.fit(V, beta, tol, max_iter, verbose, alpha, l1_ratio, precision=precision,
-                                process_group=process_group, allreduce=allreduce, unstored=unstored, solver=solver)
+                                process_group=process_group, allreduce=allreduce, unstored=unstored, weights=weights,
+                                solver=solver)
             finally:
                 w32, h32 = W.data, H.data
                 W.data, H.data = keep
@@ -522,7 +552,12 @@ class BaseComponent(nn.Module):
         V = V.detach()
         if V.dtype != torch.float32:
             V = V.float()
-        if solver == 'ccd':
+        if weights is not None:
+            from .wmu import WeightedMU
+            if not (W.data.is_contiguous() and H.data.is_contiguous()):
+                W.data, H.data = W.data.contiguous(), H.data.contiguous()
+            eng = WeightedMU(V, weights, W.data, H.data, beta, l1, l2, update_W=W.requires_grad, update_H=H.requires_grad)
+        elif solver == 'ccd':
             if not (W.data.is_contiguous() and H.data.is_contiguous()):
                 W.data, H.data = W.data.contiguous(), H.data.contiguous()
             if weight is not None:
