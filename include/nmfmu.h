@@ -82,6 +82,9 @@ extern "C" {
                                   nmfmu_wmu_terms / nmfmu_wmu_step / nmfmu_wmu_loss / nmfmu_wmu_ws / nmfmu_wmu_nsplit /
                                   nmfmu_wmu_loss_parts (NMF.fit(V, weights=M): dense per-entry weights or a dense mask on one
                                   fused exact-fp32 MFMA kernel; added at ABI 10, additive);
+                                  nmfmu_bmu_terms / nmfmu_bmu_step / nmfmu_bmu_loss / nmfmu_bmu_v_term / nmfmu_bmu_judge / nmfmu_bmu_ws /
+                                  nmfmu_bmu_nsplit / nmfmu_bmu_loss_parts (batched.BatchedNMF: many problems of one shape per
+                                  launch, each stopped on the device; added at ABI 10, additive);
                                10: nmfmu_plca_normalize / nmfmu_plca_z / nmfmu_plca3 take alpha as double (an argument changed its
                                   type: not additive).  The Dirichlet prior adds fp32(alpha - 1) with the subtraction in double,
                                   as the reference's in-place add does; fp32(alpha) - 1.f was off by 4.7e-5 relative at
@@ -847,6 +850,55 @@ int nmfmu_wmu_step(const float* V, const float* M, int64_t ld, int n, int c, int
 int nmfmu_wmu_loss_parts(int n, int c);
 int nmfmu_wmu_loss(const float* V, const float* M, int64_t ld, int n, int c, const float* H, const float* W, int rank,
                    float beta, double v_term, double* part, double* out, void* stream);
+
+/* ---- batched NMF: `batch` independent problems of one shape per launch, each stopped on its own (additive entries) ------------
+ * Problem b: V_b [n][c] fp32, row stride ld, at V + b * v_batch_stride floats (v_batch_stride == 0: ONE target shared by every
+ * problem -- restarts), H_b [n][rank] and W_b [c][rank] contiguous fp32 masters, the factors of the batch stored
+ * [batch][rows][rank].  The unweighted update of nmf.py:61-92 per problem on the tile arithmetic of the nmfmu_wmu entries
+ * (exact fp32 MFMA, y over the full padded rank, both contractions in registers; side 0: owner = H, side 1: owner = W with V
+ * walked along its columns in place; 16-byte loads of V when ld % 4 == 0, v_batch_stride % 4 == 0 and V is 16-byte aligned).
+ * The contraction is cut into parts by nmfmu_bmu_nsplit(owner rows, contraction, r_pad) == nmfmu_wmu_nsplit of the same
+ * arguments: THE BATCH DOES NOT ENTER, so the bits of a problem do not depend on how many others are fitted alongside it.
+ * ws is [problem][part][num | den][owner rows][r_pad], written with plain stores and added in part order by a second kernel:
+ * no atomics, a repeated call is bitwise identical whatever ws held.  The problem index is the slow part of grid.x; a batch
+ * whose grid.x would pass 2^31 - 1 workgroups is refused with NMFMU_ERR_UNSUPPORTED (the 65 535 limit of y / z never sees it).
+ * active: NULL (every problem) or int32 [batch] on the device; every kernel leaves at once for a problem whose flag is 0 --
+ * neither its factors, its slice of ws, its partials nor its `out` are touched.
+ *   nmfmu_bmu_ws         : floats of `ws` = batch * parts * 2 * rows * r_pad (0 if an argument is bad)
+ *   nmfmu_bmu_terms      : num, den [batch][owner rows][r_pad]; every element of an active problem is written, the padded
+ *                          columns with 0.  den - num is the gradient of the problem's loss with respect to its owner.
+ *   nmfmu_bmu_step       : the same terms, then nmf.py:78-92 in place on the owners.  owner != panel.
+ *   nmfmu_bmu_loss       : out[b] = metrics.beta_div(H_b W_b^T, V_b, beta) in float64.  The terms that hold y are summed in
+ *                          double per lane, per wave, per workgroup (part: batch * nmfmu_bmu_loss_parts(n, c) doubles), then per
+ *                          problem in block order; v_term [batch] (device) carries the terms of v alone, as
+ *                          nmfmu_bmu_v_term forms them.
+ *   nmfmu_bmu_v_term     : out[b] = the sum over V_b of the terms of metrics.beta_div that hold v alone (beta 2: 0; beta 1:
+ *                          v log(v + eps) - v; beta 0: -log(v + eps) - 1; otherwise v'^beta, v' = v + eps when beta < 0), every
+ *                          term and the sum in double: one workgroup per problem, strided lanes, then a tree -- a function of
+ *                          the problem's own entries alone.  Once per fit; a shared target is one problem (batch = 1).
+ *   nmfmu_bmu_judge      : the stop rule of nmf.py:402-407 in double, one thread per active problem: loss = sqrt(2 div[b]) (NaN
+ *                          when div[b] < 0: such a problem never stops); if (previous[b] - loss) / loss_init[b] < tol the
+ *                          problem stops: n_iter[b] = iteration + 1, active[b] = 0; otherwise previous[b] = loss.  *n_active =
+ *                          the number of problems still active.  One workgroup, no atomics.
+ * Null pointers (active may be NULL except for the judge), batch, n, c, rank <= 0, ld < c, v_batch_stride < 0, side not 0 / 1,
+ * r_pad != nmfmu_pad_rank(rank), owner == panel, nsplit < 0, iteration < 0: NMFMU_ERR_ARG; rank > 256: NMFMU_ERR_UNSUPPORTED --
+ * both before any device work. */
+int nmfmu_bmu_nsplit(int rows, int contraction, int r_pad);
+int64_t nmfmu_bmu_ws(int batch, int rows, int contraction, int r_pad, int nsplit);
+int nmfmu_bmu_terms(const float* V, int64_t v_batch_stride, int64_t ld, int batch, int n, int c, int side, const float* owner,
+                    const float* panel, int rank, int r_pad, float beta, int nsplit, const int32_t* active, float* ws,
+                    float* num, float* den, void* stream);
+int nmfmu_bmu_step(const float* V, int64_t v_batch_stride, int64_t ld, int batch, int n, int c, int side, float* owner,
+                   const float* panel, int rank, int r_pad, float beta, float l1, float l2, float gamma, int nsplit,
+                   const int32_t* active, float* ws, void* stream);
+int nmfmu_bmu_loss_parts(int n, int c);
+int nmfmu_bmu_loss(const float* V, int64_t v_batch_stride, int64_t ld, int batch, int n, int c, const float* H, const float* W,
+                   int rank, float beta, const double* v_term, const int32_t* active, double* part, double* out,
+                   void* stream);
+int nmfmu_bmu_v_term(const float* V, int64_t v_batch_stride, int64_t ld, int batch, int n, int c, float beta, double* out,
+                     void* stream);
+int nmfmu_bmu_judge(int batch, const double* div, const double* loss_init, double* previous, double tol, int iteration,
+                    int32_t* active, int64_t* n_iter, int32_t* n_active, void* stream);
 
 /* ---- PLCA's EM update (plca.py:248-290) -----------------------------------------------------------------------------
  * With G = Vn / (H diag(Z) W^T + eps) the factor "gradients" are (G^T H) * Z, (G W) * Z and Z.grad[r] = sum W * (G^T H);

@@ -30,57 +30,9 @@
 #include "nmfmu_fused.h"
 #include "nmfmu_mu_terms.h"
 #include "nmfmu_sparse_common.h"
+#include "nmfmu_wmu_tile.h"
 
 namespace nmfmu {
-
-constexpr int kWmBK = 32;            // contraction steps per stage; a part is a whole number of stages
-constexpr int kWmRows = 128;         // owner rows per workgroup
-constexpr int kWmLDA = kWmBK + 1;    // sv / sm [i][c]: lanes read a column (second product) or a row (elementwise) conflict free
-constexpr int kWmTargetWgs = 512;    // two workgroups on each of the 256 CUs
-constexpr int kWmMinStages = 4;      // the library's own parts are at least 128 contraction steps long ...
-constexpr int kWmMaxSplit = 64;      // ... and there are at most 64 of them
-
-template <int RP>
-struct WmuCfg {
-  static constexpr int RT = RP < 128 ? RP : 128;   // rank tile of the two accumulators (grid.y tiles cover r_pad)
-  static constexpr int WN = RT >= 64 ? 2 : 1;      // waves across the rank tile
-  static constexpr int WM = 4 / WN;                // waves across the 128 owner rows
-  static constexpr int TM = 4 / WM;                // 32 x 32 tiles per wave along the rows
-  static constexpr int TN = RT / (WN * 32);        // ... and along the rank
-  static constexpr int LDB = RP + 1;               // sb [c][r]: the first product reads a column of it per lane
-};
-
-static int wmu_stages(int contraction) { return (contraction + kWmBK - 1) / kWmBK; }
-
-// parts for a wanted split count >= 1: no empty part, only the last one may be short
-static int wmu_parts(int contraction, int nsplit) {
-  const int stages = wmu_stages(contraction);
-  const int n = std::max(1, std::min(nsplit, stages));
-  const int per = (stages + n - 1) / n;
-  return (stages + per - 1) / per;
-}
-static int wmu_part_len(int contraction, int parts) { return (wmu_stages(contraction) + parts - 1) / parts * kWmBK; }
-
-static int wmu_auto_split(int64_t tiles, int contraction) {
-  const int64_t want = (kWmTargetWgs + tiles - 1) / tiles;
-  const int cap = std::max(1, wmu_stages(contraction) / kWmMinStages);
-  return wmu_parts(contraction, (int)std::min<int64_t>(std::min<int64_t>(want, cap), kWmMaxSplit));
-}
-static int wmu_split(int rows, int contraction, int r_pad, int nsplit) {
-  if (nsplit > 0) return wmu_parts(contraction, nsplit);
-  return wmu_auto_split((int64_t)((rows + kWmRows - 1) / kWmRows) * ((r_pad + 127) / 128), contraction);
-}
-
-// ---- the pieces the step kernel and the loss kernel share ------------------------------------------------------------------
-// the lane's owner row (row 32 wave + j of the tile), rank slots 2 s + hl: the A operand of the first product
-template <int RP>
-__device__ __forceinline__ void wmu_load_owner(float (&a)[RP / 2], const float* owner, int rows, int rank, int row, int hl) {
-#pragma unroll
-  for (int s = 0; s < RP / 2; ++s) {
-    const int r = 2 * s + hl;
-    a[s] = (row < rows && r < rank) ? owner[(size_t)row * rank + r] : 0.f;
-  }
-}
 
 // A stage's V / M (128 x 32 each) and panel rows (32 x r_pad) on their way from HBM to LDS: 4 x 4 + 4 x 4 + r_pad / 8 registers
 // per thread.  Loaded one stage ahead, so the loads are in flight while the MFMAs of the current stage run.
@@ -132,41 +84,6 @@ __device__ __forceinline__ void wmu_store_vm(float* sv, float* sm, const WmuStag
     }
   }
 }
-
-// bv -> sb [c][r] = panel[c0 + c][r] over the full padded rank; zero in the padded columns and past the part
-template <int RP>
-__device__ __forceinline__ void wmu_load_panel(WmuStage<RP>& st, const float* __restrict__ panel, int rank, int c0, int cend,
-                                               int tid) {
-#pragma unroll
-  for (int p = 0; p < kWmBK * RP / 256; ++p) {
-    const int idx = p * 256 + tid;
-    const int c = c0 + idx / RP, r = idx % RP;
-    st.bv[p] = (c < cend && r < rank) ? panel[(size_t)c * rank + r] : 0.f;
-  }
-}
-
-template <int RP>
-__device__ __forceinline__ void wmu_store_panel(float* sb, const WmuStage<RP>& st, int tid) {
-#pragma unroll
-  for (int p = 0; p < kWmBK * RP / 256; ++p) {
-    const int idx = p * 256 + tid;
-    sb[(idx / RP) * WmuCfg<RP>::LDB + idx % RP] = st.bv[p];
-  }
-}
-
-// Y[row (e & 3) + 8 (e >> 2) + 4 hl of the wave's 32][contraction step j] = sum_r owner[row][r] panel[c0 + j][r], r ascending
-template <int RP>
-__device__ __forceinline__ f32x16 wmu_form_y(const float (&a)[RP / 2], const float* sb, int j, int hl) {
-  f32x16 y;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) y[e] = 0.f;
-  const float* pb = sb + j * WmuCfg<RP>::LDB + hl;
-#pragma unroll
-  for (int s = 0; s < RP / 2; ++s) y = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], pb[2 * s], y, 0, 0, 0);
-  return y;
-}
-
-__device__ __forceinline__ int wmu_tile_row(int e, int hl) { return (e & 3) + 8 * (e >> 2) + 4 * hl; }
 
 // grid = (row tiles, rank tiles, parts).  on / od + part * pstride: the part's planes [rows][RP].
 template <int RP, bool TRANS, int KIND>
@@ -317,17 +234,6 @@ __global__ void __launch_bounds__(256) wmu_loss_kernel(const float* __restrict__
 using namespace nmfmu;
 
 namespace {
-// f(std::integral_constant<int, r_pad>)
-template <class F>
-void for_rp(int r_pad, F&& f) {
-  switch (r_pad) {
-    case 32: f(std::integral_constant<int, 32>{}); break;
-    case 64: f(std::integral_constant<int, 64>{}); break;
-    case 128: f(std::integral_constant<int, 128>{}); break;
-    default: f(std::integral_constant<int, 256>{}); break;
-  }
-}
-
 // NMFMU_OK or the answer the entries give before any device work
 int wmu_check(const void* V, const void* M, int64_t ld, int n, int c, const void* owner, const void* panel, int rank,
               int r_pad, bool has_r_pad) {

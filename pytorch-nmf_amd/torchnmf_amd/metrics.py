@@ -24,6 +24,9 @@ were not in the training target, with ``W`` fixed.
 ``weighted_beta_div(H, W, V, weights, beta)`` (``wmu.py``) is the divergence between ``H @ W.T`` and a DENSE target with dense
 per-entry weights (a mask, exposures, confidences), for any beta, without the ``N x C`` product and differentiable with respect
 to both factors (``nmfmu_wmu_loss`` / ``nmfmu_wmu_terms``): the loss ``NMF.fit(V, weights=...)`` minimises.
+
+``batched_beta_div(H, W, V, beta)`` (``batched.py``) is ``beta_div`` for every problem of a batch ``H [B, N, R]``, ``W [B, C, R]``
+at once, float64 ``[B]``, without the ``B`` reconstructions (``nmfmu_bmu_loss``): the loss ``BatchedNMF.fit`` tracks.
 """
 from __future__ import annotations
 
@@ -35,9 +38,11 @@ from .sparse_autograd import SparseTarget, sparse_beta_div
 from .scoring import rank_scores, ranking_metrics, score_pairs, topk_scores
 from .fold_in import fold_in, fold_in_cd
 from .wmu import WeightedTarget, weighted_beta_div
+from .batched import batched_beta_div
 
 __all__ = ['kl_div', 'euclidean', 'is_div', 'beta_div', 'sparseness', 'SparseTarget', 'sparse_beta_div', 'score_pairs',
-           'topk_scores', 'rank_scores', 'ranking_metrics', 'fold_in', 'fold_in_cd', 'WeightedTarget', 'weighted_beta_div']
+           'topk_scores', 'rank_scores', 'ranking_metrics', 'fold_in', 'fold_in_cd', 'WeightedTarget', 'weighted_beta_div',
+           'batched_beta_div']
 
 
 def _beta_div_value(input: Tensor, target: Tensor, beta: float) -> Tensor:

@@ -704,6 +704,39 @@ class NMF(BaseComponent):
             return _ReconstructFn.apply(H, W)
         return _reconstruct_forward(H, W)
 
+    @torch.no_grad()
+    def fit_restarts(self, V: Tensor, n_init: int, beta: float = 1, tol: float = 1e-4, max_iter: int = 200,
+                     alpha: float = 0, l1_ratio: float = 0, generator: Optional[torch.Generator] = None):
+        """``n_init`` fits of the same dense fp32 ``V`` from different starts in one batched run (``batched.BatchedNMF`` on the
+        shared target, exact fp32, every start stopped on its own by ``fit``'s rule); the best start's factors are stored.
+
+        The first start is the module's current factors; the others are drawn from ``|N(0, 1)|`` with ``generator`` (on the
+        generator's device, the CPU by default), trainable factors only -- a frozen factor is shared by every start.  Returns
+        ``(n_iter, losses, best)``: the iteration counts (int64 ``[n_init]``) and final divergences (float64 ``[n_init]``) on
+        the CPU and the index of the smallest loss, whose factors the module now holds.  ``fit`` itself is untouched."""
+        from .batched import BatchedNMF
+        n_init = int(n_init)
+        if n_init < 1:
+            raise ValueError(f'n_init must be >= 1, got {n_init}')
+        W, H = self.W, self.H
+        assert W is not None and H is not None
+
+        def starts(p):
+            first = p.data.detach().float()
+            if n_init == 1 or not p.requires_grad:
+                return first[None].expand(n_init, *p.shape).contiguous()
+            where = generator.device if generator is not None else 'cpu'
+            drawn = torch.randn(n_init - 1, *p.shape, generator=generator, device=where).abs()
+            return torch.cat([first[None], drawn.to(first.device)])
+        bm = BatchedNMF(W=starts(W), H=starts(H), trainable_W=W.requires_grad, trainable_H=H.requires_grad).to(H.device)
+        n_iter = bm.fit(V, beta=beta, tol=tol, max_iter=max_iter, alpha=alpha, l1_ratio=l1_ratio)
+        losses = bm.last_loss.cpu()
+        best = int(torch.where(torch.isnan(losses), torch.full_like(losses, float('inf')), losses).argmin())
+        W.data.copy_(bm.W.data[best])
+        H.data.copy_(bm.H.data[best])
+        self.last_precision = bm.last_precision
+        return n_iter, losses, best
+
     def predict(self, rows: Tensor, cols: Tensor) -> Tensor:
         """The model's value at (row, column) pairs, fp32 ``[n]``, without the ``N x C`` reconstruction
         (``scoring.score_pairs`` on ``H``, ``W``; detached)."""
