@@ -85,6 +85,9 @@ extern "C" {
                                   nmfmu_bmu_terms / nmfmu_bmu_step / nmfmu_bmu_loss / nmfmu_bmu_v_term / nmfmu_bmu_judge / nmfmu_bmu_ws /
                                   nmfmu_bmu_nsplit / nmfmu_bmu_loss_parts (batched.BatchedNMF: many problems of one shape per
                                   launch, each stopped on the device; added at ABI 10, additive);
+                                  nmfmu_bwmu_terms / nmfmu_bwmu_step / nmfmu_bwmu_loss / nmfmu_bwmu_v_term (the batched entries with
+                                  per-problem dense weights and a per-problem regulariser: weighted BatchedNMF and
+                                  model_selection.cross_validate; added at ABI 10, additive);
                                10: nmfmu_plca_normalize / nmfmu_plca_z / nmfmu_plca3 take alpha as double (an argument changed its
                                   type: not additive).  The Dirichlet prior adds fp32(alpha - 1) with the subtraction in double,
                                   as the reference's in-place add does; fp32(alpha) - 1.f was off by 4.7e-5 relative at
@@ -899,6 +902,39 @@ int nmfmu_bmu_v_term(const float* V, int64_t v_batch_stride, int64_t ld, int bat
                      void* stream);
 int nmfmu_bmu_judge(int batch, const double* div, const double* loss_init, double* previous, double tol, int iteration,
                     int32_t* active, int64_t* n_iter, int32_t* n_active, void* stream);
+
+/* ---- batched NMF with per-problem weights and a per-problem regulariser (additive entries) -------------------------------------
+ * The nmfmu_bmu entries with dense weights: problem b reads M_s [n][c] fp32, V's row stride ld, at M + s * m_batch_stride floats,
+ * s = m_index[b] when m_index (int32 [batch] on the device, values validated by the caller) is given, else s = b;
+ * m_batch_stride == 0: one weight matrix for every problem.  Cross-validation shares K fold masks among K x starts x alphas
+ * problems through m_index and the target through v_batch_stride == 0: nothing of size batch x n x c exists.  The arithmetic is
+ * the nmfmu_wmu entries' per problem -- both seeds multiplied by m, an entry with m == 0 SELECTED away (V may hold NaN, Inf or
+ * a negative value there), the same tile, part order and apply: problem b of nmfmu_bwmu_terms / _step is bitwise
+ * nmfmu_wmu_terms / _step on (V_b, M_b) with the same nsplit.  A problem's bits do not depend on the batch, its position in
+ * it, or whether V or M are shared or indexed.  16-byte loads of V and M when ld, both batch strides and both bases allow,
+ * scalar loads otherwise.  ws, the split and the loss partials are nmfmu_bmu_ws / nmfmu_bmu_nsplit / nmfmu_bmu_loss_parts'
+ * (neither the batch nor the weights enter the split); nmfmu_bmu_judge serves unchanged.  An inactive problem is not touched.
+ *   reg (nmfmu_bwmu_step) : NULL, or fp32 [batch][2] on the device: problem b's (l1, l2), replacing the scalars -- one launch
+ *                           sweeps the regulariser.
+ *   M == NULL             : the unweighted kernels: bitwise the nmfmu_bmu entries (reg still honoured).
+ *   nmfmu_bwmu_loss       : out[b] = sum_ij m_ij (the term of metrics.beta_div at (i, j)) in float64, summed as nmfmu_bmu_loss.
+ *   nmfmu_bwmu_v_term     : out[b] = sum m (the terms of metrics.beta_div that hold v alone) over problem b's weighted entries,
+ *                           every term, the product and the sum in double, in nmfmu_bmu_v_term's fixed order: a function of
+ *                           (V_b, M_b) alone.
+ * The argument errors of the nmfmu_bmu entries, and m_batch_stride < 0 or m_index given with M == NULL: NMFMU_ERR_ARG -- before
+ * any device work. */
+int nmfmu_bwmu_terms(const float* V, int64_t v_batch_stride, const float* M, int64_t m_batch_stride, const int32_t* m_index,
+                     int64_t ld, int batch, int n, int c, int side, const float* owner, const float* panel, int rank, int r_pad,
+                     float beta, int nsplit, const int32_t* active, float* ws, float* num, float* den, void* stream);
+int nmfmu_bwmu_step(const float* V, int64_t v_batch_stride, const float* M, int64_t m_batch_stride, const int32_t* m_index,
+                    int64_t ld, int batch, int n, int c, int side, float* owner, const float* panel, int rank, int r_pad,
+                    float beta, float l1, float l2, const float* reg, float gamma, int nsplit, const int32_t* active, float* ws,
+                    void* stream);
+int nmfmu_bwmu_loss(const float* V, int64_t v_batch_stride, const float* M, int64_t m_batch_stride, const int32_t* m_index,
+                    int64_t ld, int batch, int n, int c, const float* H, const float* W, int rank, float beta,
+                    const double* v_term, const int32_t* active, double* part, double* out, void* stream);
+int nmfmu_bwmu_v_term(const float* V, int64_t v_batch_stride, const float* M, int64_t m_batch_stride, const int32_t* m_index,
+                      int64_t ld, int batch, int n, int c, float beta, double* out, void* stream);
 
 /* ---- PLCA's EM update (plca.py:248-290) -----------------------------------------------------------------------------
  * With G = Vn / (H diag(Z) W^T + eps) the factor "gradients" are (G^T H) * Z, (G W) * Z and Z.grad[r] = sum W * (G^T H);

@@ -1,8 +1,9 @@
 // The tile pieces the exact-fp32 MFMA kernels on the fp32 masters share: the weighted dense kernels (nmfmu_wmu.hip) and their
-// batched, unweighted siblings (nmfmu_bmu.hip).  A workgroup (4 waves) owns 128 owner rows x a rank tile of <= 128 x one part
-// of the contraction axis; a stage is 32 contraction steps.  Here: the tile plan (WmuCfg), the split rule of the contraction,
-// the owner rows in registers, the panel rows on their way to LDS, Y = owner x panel over the full padded rank, and the
-// dispatch over the padded rank.  What a kernel does with V (and M), its seeds and its epilogue stay in its own file.
+// batched siblings, unweighted and weighted (nmfmu_bmu.hip).  A workgroup (4 waves) owns 128 owner rows x a rank tile of
+// <= 128 x one part of the contraction axis; a stage is 32 contraction steps.  Here: the tile plan (WmuCfg), the split rule of
+// the contraction, the owner rows in registers, the panel rows on their way to LDS, Y = owner x panel over the full padded
+// rank, the weighted stage (V and M on their way to LDS) and the dispatch over the padded rank.  A kernel's seeds and its
+// epilogue stay in its own file.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -96,6 +97,57 @@ __device__ __forceinline__ f32x16 wmu_form_y(const float (&a)[RP / 2], const flo
 }
 
 __device__ __forceinline__ int wmu_tile_row(int e, int hl) { return (e & 3) + 8 * (e >> 2) + 4 * hl; }
+
+// A stage's V / M (128 x 32 each) and panel rows (32 x r_pad) on their way from HBM to LDS: 4 x 4 + 4 x 4 + r_pad / 8 registers
+// per thread.  Loaded one stage ahead, so the loads are in flight while the MFMAs of the current stage run.
+template <int RP>
+struct WmuStage {
+  float av[4][4], mv[4][4], bv[kWmBK * RP / 256];
+};
+
+// av / mv = V / M at (owner row i0 + i, contraction step c0 + c); zero outside the matrix and the part (m = 0: the entry is
+// selected away).  16-byte loads along the walk's contiguous axis when `vec`, else scalar loads.
+template <int RP, bool TRANS>
+__device__ __forceinline__ void wmu_load_vm(WmuStage<RP>& st, const float* __restrict__ V, const float* __restrict__ M,
+                                            int64_t ld, int rows, int i0, int c0, int cend, bool vec, int tid) {
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    const int idx = p * 256 + tid;
+    float* av = st.av[p];
+    float* mv = st.mv[p];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) av[q] = mv[q] = 0.f;
+    // TRANS: V[c0 + cr][i0 + i4 ..], contiguous along i; else V[i0 + row][c0 + c4 ..], contiguous along c
+    const int c = c0 + (TRANS ? idx >> 5 : (idx & 7) * 4), i = i0 + (TRANS ? (idx & 31) * 4 : idx >> 3);
+    if (c < cend && i < rows) {
+      const size_t off = TRANS ? (size_t)c * ld + i : (size_t)i * ld + c;
+      const int left = TRANS ? rows - i : cend - c;      // elements of the quad inside the matrix and the part
+      if (vec && left >= 4) {
+        const float4 v = *reinterpret_cast<const float4*>(V + off), m = *reinterpret_cast<const float4*>(M + off);
+        av[0] = v.x, av[1] = v.y, av[2] = v.z, av[3] = v.w;
+        mv[0] = m.x, mv[1] = m.y, mv[2] = m.z, mv[3] = m.w;
+      } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          if (q < left) av[q] = V[off + q], mv[q] = M[off + q];
+      }
+    }
+  }
+}
+
+// sv / sm [i][c], a row stride of 33 floats for either walk
+template <int RP, bool TRANS>
+__device__ __forceinline__ void wmu_store_vm(float* sv, float* sm, const WmuStage<RP>& st, int tid) {
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    const int idx = p * 256 + tid;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int at = TRANS ? ((idx & 31) * 4 + q) * kWmLDA + (idx >> 5) : (idx >> 3) * kWmLDA + (idx & 7) * 4 + q;
+      sv[at] = st.av[p][q], sm[at] = st.mv[p][q];
+    }
+  }
+}
 
 // f(std::integral_constant<int, r_pad>)
 template <class F>

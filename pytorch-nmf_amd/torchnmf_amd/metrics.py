@@ -26,7 +26,9 @@ per-entry weights (a mask, exposures, confidences), for any beta, without the ``
 to both factors (``nmfmu_wmu_loss`` / ``nmfmu_wmu_terms``): the loss ``NMF.fit(V, weights=...)`` minimises.
 
 ``batched_beta_div(H, W, V, beta)`` (``batched.py``) is ``beta_div`` for every problem of a batch ``H [B, N, R]``, ``W [B, C, R]``
-at once, float64 ``[B]``, without the ``B`` reconstructions (``nmfmu_bmu_loss``): the loss ``BatchedNMF.fit`` tracks.
+at once, float64 ``[B]``, without the ``B`` reconstructions (``nmfmu_bmu_loss``): the loss ``BatchedNMF.fit`` tracks.  With
+``weights`` (and ``weight_index``) it is the weighted divergence per problem (``nmfmu_bwmu_loss``): what
+``BatchedNMF.fit(V, weights=...)`` tracks and ``model_selection.cross_validate`` scores held-out entries with.
 """
 from __future__ import annotations
 

@@ -713,7 +713,10 @@ class NMF(BaseComponent):
         The first start is the module's current factors; the others are drawn from ``|N(0, 1)|`` with ``generator`` (on the
         generator's device, the CPU by default), trainable factors only -- a frozen factor is shared by every start.  Returns
         ``(n_iter, losses, best)``: the iteration counts (int64 ``[n_init]``) and final divergences (float64 ``[n_init]``) on
-        the CPU and the index of the smallest loss, whose factors the module now holds.  ``fit`` itself is untouched."""
+        the CPU and the index of the smallest loss, whose factors the module now holds.  ``fit`` itself is untouched.
+
+        Restarts of a WEIGHTED fit are ``batched.BatchedNMF.fit(V, weights=M)`` on the shared target and the shared weights;
+        choosing the rank or ``alpha`` by held-out loss is ``model_selection.cross_validate``."""
         from .batched import BatchedNMF
         n_init = int(n_init)
         if n_init < 1:
