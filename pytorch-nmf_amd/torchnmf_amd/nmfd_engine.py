@@ -159,7 +159,7 @@ class ConvPlan:
     w_ksplit: int
     stage_mode: int          # nmfmu_gemm_desc.stage_mode: 0 stages implicit operands as windows where the library admits it
     # 'f16' (fp16 operand planes, window tables and ratio planes: 11 significant bits at the bf16 MFMA rate) exists for beta == 1
-    # on aligned shapes whose H numerator takes the fold-parts or the window-operand path; 'auto' asks the data (f16_auto) where
+    # on window tables (implicit) whose H numerator takes the fold-parts or the window-operand path; 'auto' asks the data (f16_auto) where
     # every contraction is long enough for the rounding errors to average down, and tells the user
     # (f16_warn) when unaligned taps / frames alone cost the fast mode
     f16_ok: bool
@@ -230,13 +230,11 @@ def plan_conv(lib, B, C, ls, R, ts, beta, own_loop=True, ncu=256, env=None) -> C
     elif on('KSPLIT'):
         w_ksplit = w_contraction_split(tiles, kt_w, slots)
     # 'f16' in two forms: the fold-parts path with fused sums (Y elements contract over the channels alone) and the
-    # window-operand path (over channels x taps).
-    # NOTE: admission asks for `aligned`, not for `implicit`: with window tables of 2 GiB or more 'f16' is admitted on explicit
-    # planes, which nmfmu_conv_unfold writes as bf16.  Nobody has run that case.  The rule is kept as it was found: mending it
-    # changes behaviour and is a change of its own.
+    # window-operand path (over channels x taps).  Only on window tables (`implicit`): explicit planes are written as bf16
+    # (nmfmu_conv_unfold), also where aligned taps and frames lose their tables to the 2 GiB limit.
     f16_fold = nd == 1 and T >= 128 and on('FOLD_PARTS') and on('FUSED_SUMS')
     f16_rows = (nd > 1 or 1 < T < 128) and on('H_ROWS')
-    f16_ok = own_loop and kl and aligned and (f16_fold or f16_rows) and (fold_parts or h_rows)
+    f16_ok = own_loop and kl and implicit and (f16_fold or f16_rows) and (fold_parts or h_rows)
     long_fold = min(C, B * L) >= F16_MIN_DIM and R * T >= F16_MIN_DIM
     long_enough = long_fold if f16_fold else min(C * T, B * L, R * T) >= F16_MIN_DIM
     return ConvPlan(

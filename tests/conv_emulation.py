@@ -452,6 +452,16 @@ def plan(case, ncu):
     return dict(p, h_tail=(p['h_tail_rows'], p['h_tail_split']))
 
 
+def signature(p):
+    """What a plan (a ConvPlan as a dict) decides, without sizes, contraction splits and beta: (shift axes, implicit, H path,
+    ragged channels, c_rows, fused_sums, fused_tables, rows_fused, wk_fold).  test_conv_emulation.py holds the plans of a
+    default-switch grid against the case list by it."""
+    h_path = 'fold_parts' if p['fold_parts'] else 'h_rows' if p['h_rows'] else 'store_y'
+    rag = 'in_grid' if p['ragged_in_grid'] else 'ragged' if p['ragged'] else None
+    return (p['nd'], bool(p['implicit']), h_path, rag, p['c_rows'], bool(p['fused_sums']), bool(p['fused_tables']),
+            bool(p['rows_fused']), p['wk_fold'])
+
+
 def claim_holds(claim, p, case):
     """Does the plan reach the control flow ``claim`` names?  A claim is 'flag' (truthy), '!flag' (falsy) or 'flag=value'."""
     if '=' in claim:
@@ -557,6 +567,70 @@ def conv_cases():
     for prec, beta in (('bf16x3', 1), ('f16', 1), ('bf16', 2), ('bf16x3', 0.5)):
         add('ragged-in-grid', 1, 1025, 1024, 2, 128, prec, beta, ('ragged', 'ragged_in_grid', 'fold_parts'),
             staged=dict(recon_w=1, recon_h=1, num_w=1))
+    # ---- the plans the default switches reach on small shapes and the cases above do not: one case or more per signature
+    # (``signature``; test_conv_emulation.py holds the list against a grid of default plans).  Per (shift axes, operand
+    # form, H path): beta 1, 2 and a third, split and single bf16, 'f16' where the plan admits it; rows_fused is beta == 1.
+    EXP, ROWS = ('!implicit', 'h_rows'), ('implicit', 'h_rows')
+    fold = lambda f: ('wk_fold=%d' % f,)
+    # one shift axis.  Explicit planes with the window-operand numerator: tap folds 2 / 4, ragged channels at folds 1 / 2
+    add('explicit-fold2', 2, 20, 50, 2, 6, 'bf16x3', 1, EXP + fold(2) + ('!ragged', 'batch_in_tile'))
+    add('explicit-fold4', 1, 20, 203, 2, 16, 'bf16', 2, EXP + fold(4) + ('!ragged',))
+    add('explicit-ragged-fold1', 1, 129, 61, 2, 5, 'bf16x3', 0.5, EXP + fold(1) + ('ragged', '!ragged_in_grid'))
+    add('explicit-ragged-fold2', 1, 129, 50, 2, 6, 'bf16', 1, EXP + fold(2) + ('ragged', '!ragged_in_grid'))
+    add('explicit-ragged-fold2', 1, 129, 50, 2, 6, 'bf16x3', 2, EXP + fold(2) + ('ragged', '!ragged_in_grid'), regs=REG)
+    # the unfused fold-parts kernel beside a ragged channel (beta == 1: with the fused sums switched off)
+    FRAG = ('implicit', 'fold_parts', '!fused_sums', '!fused_tables', 'ragged', '!ragged_in_grid')
+    add('fold-ragged-unfused', 1, 129, 256, 2, 128, 'bf16x3', 2, FRAG)
+    add('fold-ragged-unfused', 1, 129, 256, 2, 128, 'bf16', 1.5, FRAG)
+    add('fold-ragged-unfused', 1, 129, 256, 2, 128, 'bf16x3', 1, FRAG, env={'FUSED_SUMS': '0'}, regs=REG)
+    # window tables with the window-operand numerator: rows_fused at fold 1; ragged channels at folds 1 / 2 (8 taps) and,
+    # with rows_fused, at folds 1 / 2 / 4 (64 taps)
+    add('rows-fused-fold1', 1, 20, 128, 40, 64, 'bf16x3', 1, ROWS + fold(1) + ('rows_fused', '!ragged'))
+    add('rows-ragged-fold1', 1, 129, 96, 40, 8, 'bf16x3', 2, ROWS + fold(1) + ('ragged', '!rows_fused'))
+    add('rows-ragged-fold1', 1, 129, 96, 40, 8, 'bf16', 1, ROWS + fold(1) + ('ragged', '!rows_fused'), regs=REG)
+    add('rows-ragged-fold2', 1, 129, 96, 11, 8, 'bf16', 1.5, ROWS + fold(2) + ('ragged', '!rows_fused'))
+    add('rows-ragged-fold2', 1, 129, 96, 11, 8, 'f16', 1, ROWS + fold(2) + ('ragged', '!rows_fused'))
+    add('rows-ragged-fused-fold1', 1, 129, 128, 40, 64, 'bf16x3', 1, ROWS + fold(1) + ('ragged', 'rows_fused'), regs=REG)
+    add('rows-ragged-fused-fold2', 1, 129, 128, 11, 64, 'bf16', 1, ROWS + fold(2) + ('ragged', 'rows_fused'))
+    add('rows-ragged-fused-fold4', 1, 129, 128, 2, 64, 'f16', 1, ROWS + fold(4) + ('ragged', 'rows_fused'))
+    # two shift axes.  Explicit planes (last axis no multiple of 8) with the window-operand numerator: folds 1 / 2 / 4
+    add('explicit-2d-fold1', 2, 20, (12, 31), 2, (2, 5), 'bf16x3', 1, EXP + fold(1) + ('!c_rows', 'batch_in_tile'))
+    add('explicit-2d-fold1', 2, 20, (12, 31), 2, (2, 5), 'bf16', 0.5, EXP + fold(1) + ('!c_rows', 'batch_in_tile'), regs=REG)
+    add('explicit-2d-fold2', 1, 20, (14, 19), 11, (3, 4), 'bf16', 2, EXP + fold(2) + ('!c_rows',))
+    add('explicit-2d-fold4', 1, 20, (14, 19), 2, (3, 4), 'bf16x3', 2, EXP + fold(4) + ('!c_rows',), regs=REG)
+    # window tables: the 128-row and the 64-row channel tile at folds 1 / 2 (24 taps) and with rows_fused (64 taps)
+    add('rows-2d-fold1', 1, 70, (18, 24), 40, (3, 8), 'bf16x3', 2, ROWS + fold(1) + ('!c_rows', '!rows_fused'))
+    add('rows-2d-fold1', 1, 70, (18, 24), 40, (3, 8), 'f16', 1, ROWS + fold(1) + ('!c_rows', '!rows_fused'))
+    add('rows-2d-fold2', 1, 70, (18, 24), 11, (3, 8), 'bf16', 0.5, ROWS + fold(2) + ('!c_rows', '!rows_fused'), regs=REG)
+    add('rows-2d-fused-fold1', 1, 70, (30, 40), 40, (8, 8), 'bf16', 1, ROWS + fold(1) + ('!c_rows', 'rows_fused'))
+    add('rows-2d-fused-fold2', 1, 70, (30, 40), 11, (8, 8), 'bf16x3', 1, ROWS + fold(2) + ('!c_rows', 'rows_fused'))
+    add('rows-2d-fused-fold4', 1, 70, (30, 40), 2, (8, 8), 'f16', 1, ROWS + fold(4) + ('!c_rows', 'rows_fused'), regs=REG)
+    add('rows-2d-narrow-fold1', 1, 20, (18, 24), 40, (3, 8), 'bf16', 1, ROWS + fold(1) + ('c_rows', '!rows_fused'))
+    add('rows-2d-narrow-fold2', 1, 20, (18, 24), 11, (3, 8), 'bf16x3', 1.5, ROWS + fold(2) + ('c_rows', '!rows_fused'))
+    add('rows-2d-narrow-fused-fold1', 1, 20, (30, 40), 40, (8, 8), 'bf16x3', 1, ROWS + fold(1) + ('c_rows', 'rows_fused'), regs=REG)
+    add('rows-2d-narrow-fused-fold2', 1, 20, (30, 40), 11, (8, 8), 'bf16', 1, ROWS + fold(2) + ('c_rows', 'rows_fused'))
+    # three shift axes.  Explicit planes: folds 1 / 2, and fold 4 with a middle tap axis of extent 1
+    add('explicit-3d-fold1', 1, 20, (5, 7, 9), 40, (2, 3, 2), 'bf16', 2, EXP + fold(1) + ('!c_rows',))
+    add('explicit-3d-fold2', 2, 20, (5, 7, 9), 2, (2, 3, 2), 'bf16x3', 1, EXP + fold(2) + ('!c_rows', 'batch_in_tile'), regs=REG)
+    add('explicit-3d-fold2', 2, 20, (5, 7, 9), 2, (2, 3, 2), 'bf16', 1.5, EXP + fold(2) + ('!c_rows', 'batch_in_tile'))
+    add('explicit-3d-fold4', 1, 20, (4, 5, 11), 2, (2, 1, 4), 'bf16x3', 2, EXP + fold(4) + ('!c_rows',), regs=REG)
+    # window tables: both channel tiles at folds 1 / 2 / 4 (48 taps) and with rows_fused (64 taps)
+    add('rows-3d-wide-fold1', 1, 70, (6, 9, 16), 40, (2, 3, 8), 'bf16x3', 1, ROWS + fold(1) + ('!c_rows', '!rows_fused'))
+    add('rows-3d-wide-fold2', 1, 70, (6, 9, 16), 11, (2, 3, 8), 'bf16', 2, ROWS + fold(2) + ('!c_rows', '!rows_fused'))
+    add('rows-3d-wide-fold4', 1, 70, (6, 9, 16), 2, (2, 3, 8), 'f16', 1, ROWS + fold(4) + ('!c_rows', '!rows_fused'), regs=REG)
+    add('rows-3d-wide-fused-fold1', 1, 70, (5, 6, 32), 40, (2, 2, 16), 'bf16', 1, ROWS + fold(1) + ('!c_rows', 'rows_fused'))
+    add('rows-3d-wide-fused-fold2', 1, 70, (5, 6, 32), 11, (2, 2, 16), 'f16', 1, ROWS + fold(2) + ('!c_rows', 'rows_fused'))
+    add('rows-3d-wide-fused-fold4', 1, 70, (5, 6, 32), 2, (2, 2, 16), 'bf16x3', 1, ROWS + fold(4) + ('!c_rows', 'rows_fused'), regs=REG)
+    # (the third beta of this rank-40 case in split bf16 is 1.5, not 0: the lo-word check holds a term to AMBIGUITY = 2e-6,
+    # and S summed in fp32 over its 3 x 1920 products differs from the float64 sum by 1.2e-6 on the reference side alone
+    # (numpy float32, k-chunks of 16, either order), which Gn = x S^(beta - 2) doubles at beta == 0: 2.3e-6 before the
+    # device's reciprocal, 2.3 .. 2.6e-6 in 10 of 17 280 words on the MI355X, one each in ten channels.  At beta == 1.5 the
+    # exponent is -0.5 and no word leaves the band.)
+    add('rows-3d-fold1', 1, 20, (6, 9, 16), 40, (2, 3, 8), 'bf16x3', 1.5, ROWS + fold(1) + ('c_rows', '!rows_fused'))
+    add('rows-3d-fold2', 1, 20, (6, 9, 16), 11, (2, 3, 8), 'bf16', 1, ROWS + fold(2) + ('c_rows', '!rows_fused'))
+    add('rows-3d-fused-fold1', 1, 20, (5, 6, 32), 40, (2, 2, 16), 'bf16x3', 1, ROWS + fold(1) + ('c_rows', 'rows_fused'), regs=REG)
+    add('rows-3d-fused-fold2', 1, 20, (5, 6, 32), 11, (2, 2, 16), 'bf16', 1, ROWS + fold(2) + ('c_rows', 'rows_fused'))
+    add('rows-3d-fused-fold4', 1, 20, (5, 6, 32), 2, (2, 2, 16), 'f16', 1, ROWS + fold(4) + ('c_rows', 'rows_fused'))
     return cases
 
 

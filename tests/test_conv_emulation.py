@@ -1,6 +1,7 @@
 """tests/conv_emulation.py on the CPU: the unrounded emulation IS the oracle's algorithm, unfold and fold are adjoint, the
 per-element checks of tests/test_gpu_conv_emulated_parity.py catch seeded faults that the whole-factor norm of the older GPU
-tests lets through, and the case list reaches the control flow it claims as far as the host functions can tell."""
+tests lets through, the case list reaches the control flow it claims as far as the host functions can tell and holds a case
+for every plan the default switches reach on a grid of small shapes, and 'f16' is admitted on window tables only."""
 import numpy as np
 import pytest
 import torch
@@ -236,6 +237,71 @@ def test_case_list_reaches_what_it_claims(ncu):
     assert {c['C'] % 128 for c in cases if 'ragged' in c['claims']} >= {1, 2, 8}
     for prec, betas in (('bf16x3', {1, 2, 0.5, 0, -1}), ('bf16', {1, 2, 0.5, 0, 1.5, -1}), ('f16', {1})):
         assert {c['beta'] for c in cases if c['precision'] == prec} >= betas
+
+
+# The plans a user gets with every switch at its default, over small shapes on both sides of every rule of plan_conv: taps
+# and frames aligned or not, T below / at / above 64 and 128, channels around the 64-row tile, the 128-row tile and the
+# ragged rule, ranks at each tap fold.  (T, L) / (ts, ls) per number of shift axes.
+GRID_AXES = ([((t,), (l,)) for t, l in ((5, 61), (6, 50), (8, 96), (16, 128), (16, 203), (24, 200), (64, 128), (72, 256),
+                                        (128, 256), (136, 264))] +
+             [((3, 4), (14, 19)), ((3, 8), (18, 24)), ((8, 8), (30, 40)), ((2, 5), (12, 31)), ((4, 16), (20, 48)),
+              ((8, 16), (24, 64))] +
+             [((2, 3, 8), (6, 9, 16)), ((2, 3, 2), (5, 7, 9)), ((2, 1, 4), (4, 5, 11)), ((2, 2, 16), (5, 6, 32))])
+GRID_B, GRID_C, GRID_R, GRID_BETA = (1, 2), (20, 64, 70, 129, 200), (2, 5, 11, 40), (1.0, 2.0, 0.5)
+
+
+def test_every_default_plan_on_the_grid_has_a_case():
+    """Every signature (conv_emulation.signature) that plan_conv reaches on the grid at 256 CUs with the switches at their
+    defaults is the signature of at least one case of the per-element GPU test: a plan path added later fails here until it
+    has a case."""
+    import dataclasses
+    import itertools
+    from torchnmf_amd import _capi, nmfd_engine as N
+    lib = _capi.load()
+    covered = {CE.signature(CE.plan(c, 256)) for c in CE.conv_cases()}
+    reached = {}
+    for (ts, ls), B, C, R, beta in itertools.product(GRID_AXES, GRID_B, GRID_C, GRID_R, GRID_BETA):
+        p = dataclasses.asdict(N.plan_conv(lib, B, C, ls, R, ts, beta, True, 256, env={}))
+        reached.setdefault(CE.signature(p), (B, C, ls, R, ts, beta))
+    missing = {s: ex for s, ex in reached.items() if s not in covered}
+    for s, ex in sorted(missing.items(), key=repr):
+        print('no case for', s, 'e.g. (B, C, ls, R, ts, beta) =', ex)
+    assert len(reached) >= 52                                        # (the grid still reaches what it was built to reach)
+    assert not missing, f'{len(missing)} of {len(reached)} signatures of the default-switch grid have no per-element case'
+
+
+class _TablesOf2GiB:
+    """The library with window tables of 2 GiB whatever the shape (the two table-size queries; everything else passes)."""
+
+    def __init__(self, lib):
+        self._lib = lib
+
+    def __getattr__(self, name):
+        if name in ('nmfmu_conv_table_bytes', 'nmfmu_convnd_table_bytes'):
+            return lambda *a: 2 ** 31
+        return getattr(self._lib, name)
+
+
+@pytest.mark.parametrize('shape', [(2, 70, (200,), 5, (24,)), (2, 70, (256,), 2, (128,)), (2, 20, (30, 40), 3, (8, 8))],
+                         ids=['rows-1d', 'fold-parts', 'rows-2d'])
+def test_f16_is_refused_where_the_window_tables_reach_2_gib(shape):
+    """Aligned taps and frames whose window tables reach 2 GiB get explicit planes, which are bf16: the plan is the
+    NMFD_EXPLICIT=1 plan in every field, 'f16' raises and 'auto' stays split bf16 without looking at data."""
+    import dataclasses
+    from torchnmf_amd import _capi, nmfd_engine as N
+    lib = _capi.load()
+    B, C, ls, R, ts = shape
+    small = N.plan_conv(lib, B, C, ls, R, ts, 1.0, True, 256, env={})
+    assert small.implicit and small.f16_ok                           # (the shapes are admitted while the tables are small)
+    big = N.plan_conv(_TablesOf2GiB(lib), B, C, ls, R, ts, 1.0, True, 256, env={})
+    explicit = N.plan_conv(lib, B, C, ls, R, ts, 1.0, True, 256, env={'TORCHNMF_AMD_NMFD_EXPLICIT': '1'})
+    assert not big.implicit and big.table_bytes == 0
+    for k, v in dataclasses.asdict(explicit).items():
+        assert getattr(big, k) == v, (k, getattr(big, k), v)
+    assert big.f16_ok is False and big.f16_auto is False
+    with pytest.raises(ValueError, match="precision 'f16' is built for"):
+        N.resolve_precision(big, 'f16', None, None, None)
+    assert N.resolve_precision(big, 'auto', None, None, None) == 'bf16x3'      # (no tensor to read: it did not ask)
 
 
 def test_device_planes_feed_the_numerators_and_a_silent_channel_does_not_hide_the_rest():

@@ -24,9 +24,15 @@ The numerators and the master are emulated from the ratio words the device wrote
 emulation's own choice among ambiguous neighbours, so they carry no allowance (conv_emulation.with_device_planes).  The
 silent channel's rows of num_w / den_w (1e7 times the others) are judged apart from the live rows.
 
-Measured on the MI355X (76 cases, 7 s): every ratio plane, operand image and zero exact; ambiguous share at most 0.18 %
-(bf16 / bf16x3) and 0.70 % (f16); numerators, denominators and masters at most 1.6e-6 per element (ragged-in-grid; 1.1e-6
-elsewhere) against mu_emulation.TOL of 2.5e-6 / 4e-6; loss at most 3.2e-7 relative.  No tolerance is raised.
+The case list holds a case for every plan signature (conv_emulation.signature) that the default switches reach on the
+grid of tests/test_conv_emulation.py::test_every_default_plan_on_the_grid_has_a_case.
+
+Measured on the MI355X (121 cases, 9 s): every ratio plane, operand image and zero exact; ambiguous share at most 0.18 %
+(bf16 / bf16x3) and 0.70 % (f16); numerators, denominators and masters at most 1.6e-6 per element (ragged-in-grid; 1.2e-6
+elsewhere, rows-3d-fold1 in split bf16) against mu_emulation.TOL of 2.5e-6 / 4e-6; loss at most 3.2e-7 relative.  No
+tolerance is raised.  One finding on the reference side: at rank 40 with 48 taps (3 x 1920 products per element of S) the
+fp32 sum of S alone differs from float64 by 1.2e-6, which beta == 0 doubles in Gn -- past the 2e-6 band of the lo-word
+check in 10 of 17 280 words; that case runs beta == 1.5 (the note beside it in conv_cases).
 """
 import numpy as np
 import pytest
