@@ -88,6 +88,9 @@ extern "C" {
                                   nmfmu_bwmu_terms / nmfmu_bwmu_step / nmfmu_bwmu_loss / nmfmu_bwmu_v_term (the batched entries with
                                   per-problem dense weights and a per-problem regulariser: weighted BatchedNMF and
                                   model_selection.cross_validate; added at ABI 10, additive);
+                                  nmfmu_separate / nmfmu_separate_planes / nmfmu_separate_accumulate / nmfmu_separate_max_rank / nmfmu_separate_tables_bytes
+                                  (separation.separate: per-group soft masks of a fitted model times the mixture; added at ABI 10,
+                                  additive);
                                10: nmfmu_plca_normalize / nmfmu_plca_z / nmfmu_plca3 take alpha as double (an argument changed its
                                   type: not additive).  The Dirichlet prior adds fp32(alpha - 1) with the subtraction in double,
                                   as the reference's in-place add does; fp32(alpha) - 1.f was off by 4.7e-5 relative at
@@ -1031,6 +1034,46 @@ int nmfmu_rank_pass(int pass, int form, const float* H, int N, const int32_t* ro
                     int rank, const int32_t* ho_rowptr, const int32_t* ho_colidx, const int32_t* ex_rowptr,
                     const int32_t* ex_colidx, int nsplit, void* ws, float* out_score, int32_t* out_rank,
                     int32_t* out_admissible, void* stream);
+
+/* ---- source separation: per-group soft masks of a fitted model (additive entries; separation.py) ----------
+ * With Y_g the reconstruction from the components of group g alone, D = sum_{g < groups} Y_g^power in ascending g (power == 1:
+ * the one reconstruction over all components), every output plane s holds  v * (Y_g^power / (D + eps))  for the group g with
+ * slot[g] == s.  v_kind 0: no mixture (v = 1, fp32 planes); 1: V real fp32 [n][ldv]; 2: V complex64 read as interleaved floats
+ * (ldv in complex elements), planes complex64 -- the real mask multiplies both parts.  slot [groups] (HOST) maps a group to its
+ * output plane, -1 for none; at most one group per plane is the caller's business.  Every element of every mapped plane is
+ * written; Y_g and D are never stored.
+ *   nmfmu_separate        : dense models on one fused exact-fp32 MFMA kernel (the tile of nmfmu_reconstruct).  Hp [n][cols] and
+ *                           Wp [c][cols] are the factors with the components sorted by group and every group padded with zero
+ *                           columns to an even count; gstart [groups + 1] (HOST) are the groups' first columns: gstart[0] == 0,
+ *                           gstart[groups] == cols, ascending, every entry even (an empty group has equal neighbours).  Plane s is
+ *                           out + s * n * ld (elements), row stride ld.  tables_dev: nmfmu_separate_tables_bytes(groups) bytes on
+ *                           the device that the CALLER has filled with gstart [groups + 1] followed by slot [groups]: the
+ *                           kernel reads that copy, the library validates the host arrays (read only during the call) and
+ *                           copies nothing.  16-byte loads of the factors when cols % 4 == 0 and Hp, Wp are 16-byte aligned,
+ *                           scalar otherwise; V and out must be aligned to their element (8 bytes for v_kind 2), else
+ *                           NMFMU_ERR_ARG.  groups <= nmfmu_separate_max_rank() and cols <= twice that, else
+ *                           NMFMU_ERR_UNSUPPORTED.
+ *   nmfmu_separate_planes : the planes Y_g are given: element i of plane g at Y[g * y_stride + i * y_elem], y_elem 1 or 2 (2: the
+ *                           planes sit in the real slots of a complex output).  D: NULL, or the denominator plane [n] to use
+ *                           instead of the sum.  Output plane s is out + s * out_stride (elements).  An input plane may be the
+ *                           output plane of its own group (same element positions).  slot_dev: groups * 4 bytes on the device
+ *                           that the CALLER has filled with slot (the kernel reads it; the host array is what is validated).
+ *                           16-byte accesses when every base is 16-byte aligned and the strides are multiples of four floats.
+ *   nmfmu_separate_accumulate : D[i] += Y[i * y_elem]^power for i < n, with the very operation the two kernels above use for their
+ *                           own sums (power == 2: one fused multiply-add), so a denominator accumulated plane by plane in
+ *                           ascending g from a zero plane has the bits of the one nmfmu_separate_planes forms itself.
+ * Null pointers, sizes < 1, ld / ldv below c, y_stride below n * y_elem, out_stride below n, power <= 0 or not a number, eps < 0, an
+ * unknown v_kind or y_elem, a boundary table that is not as described, a slot outside [-1, planes): NMFMU_ERR_ARG -- before any
+ * device work.  No atomics: a repeated call is bitwise identical, and a plane's bits do not depend on the other slots. */
+int nmfmu_separate_max_rank(void);
+int64_t nmfmu_separate_tables_bytes(int groups);
+int nmfmu_separate(const float* Hp, int n, const float* Wp, int c, int cols, const int32_t* gstart, const int32_t* slot,
+                   int groups, int planes, void* tables_dev, const float* V, int v_kind, int64_t ldv, float power, float eps,
+                   float* out, int64_t ld, void* stream);
+int nmfmu_separate_planes(const float* Y, int groups, int64_t y_stride, int y_elem, const float* D, const float* V, int v_kind,
+                          int64_t n, float power, float eps, const int32_t* slot, int planes, void* slot_dev, float* out,
+                          int64_t out_stride, void* stream);
+int nmfmu_separate_accumulate(const float* Y, int y_elem, int64_t n, float power, float* D, void* stream);
 
 /* ---- fold-in: new rows against a fixed W, all iterations in one launch (additive entries; fold_in.py) ----
  * The new rows come as CSR (rowptr [n_rows + 1], colidx / vals [nnz], int32 indices below n_cols); H [n_rows][rank] holds the

@@ -318,6 +318,15 @@ SIGNATURES = {
     'nmfmu_fold_parts_supported': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     'nmfmu_conv_fold_parts_apply_h': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_void_p]),
+    'nmfmu_separate_max_rank': (C.c_int, []),
+    'nmfmu_separate_tables_bytes': (C.c_int64, [C.c_int]),
+    'nmfmu_separate': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                 C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_float, C.c_void_p,
+                                 C.c_int64, C.c_void_p]),
+    'nmfmu_separate_planes': (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int64,
+                                        C.c_float, C.c_float, C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
+                                        C.c_void_p]),
+    'nmfmu_separate_accumulate': (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),
     'nmfmu_comm_available': (C.c_int, []),
     'nmfmu_comm_unique_id': (C.c_int, [C.c_void_p]),
     'nmfmu_comm_init_rank': (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_int]),

@@ -29,6 +29,9 @@ to both factors (``nmfmu_wmu_loss`` / ``nmfmu_wmu_terms``): the loss ``NMF.fit(V
 at once, float64 ``[B]``, without the ``B`` reconstructions (``nmfmu_bmu_loss``): the loss ``BatchedNMF.fit`` tracks.  With
 ``weights`` (and ``weight_index``) it is the weighted divergence per problem (``nmfmu_bwmu_loss``): what
 ``BatchedNMF.fit(V, weights=...)`` tracks and ``model_selection.cross_validate`` scores held-out entries with.
+
+``separate(H, W, V, groups, power=...)`` (``separation.py``) is what follows a fit on a spectrogram: the soft mask of every group
+of components, or the mixture (real, or the complex STFT) times it, on one fused kernel (``nmfmu_separate``).
 """
 from __future__ import annotations
 
@@ -41,10 +44,11 @@ from .scoring import rank_scores, ranking_metrics, score_pairs, topk_scores
 from .fold_in import fold_in, fold_in_cd
 from .wmu import WeightedTarget, weighted_beta_div
 from .batched import batched_beta_div
+from .separation import separate
 
 __all__ = ['kl_div', 'euclidean', 'is_div', 'beta_div', 'sparseness', 'SparseTarget', 'sparse_beta_div', 'score_pairs',
            'topk_scores', 'rank_scores', 'ranking_metrics', 'fold_in', 'fold_in_cd', 'WeightedTarget', 'weighted_beta_div',
-           'batched_beta_div']
+           'batched_beta_div', 'separate']
 
 
 def _beta_div_value(input: Tensor, target: Tensor, beta: float) -> Tensor:

@@ -223,6 +223,15 @@ class BaseComponent(nn.Module):
     def reconstruct(H: Tensor, W: Tensor) -> Tensor:
         raise NotImplementedError
 
+    def separate(self, V: Tensor = None, groups=None, *, power=1.0, select=None) -> Tensor:
+        """``separation.separate`` with the module's own factors: ``[S, *target shape]``, the soft mask of every selected
+        group of components (``groups``: ``R`` labels, default every component alone), or the mixture ``V`` (real, or the
+        ``complex64`` STFT) times it.  Detached; the module is not modified."""
+        from .separation import separate
+        assert self.H is not None
+        assert self.W is not None
+        return separate(self.H, self.W, V, groups, power=power, select=select)
+
     def _make_engine(self, V, beta, l1, l2, precision, group, allreduce=None):
         raise NotImplementedError
 
