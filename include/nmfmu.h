@@ -91,6 +91,8 @@ extern "C" {
                                   nmfmu_separate / nmfmu_separate_planes / nmfmu_separate_accumulate / nmfmu_separate_max_rank / nmfmu_separate_tables_bytes
                                   (separation.separate: per-group soft masks of a fitted model times the mixture; added at ABI 10,
                                   additive);
+                                  nmfmu_ard_apply / nmfmu_ard_relevance (NMF.fit_ard: the apply stage with a per-component
+                                  penalty and the relevance update of ARD-NMF; added at ABI 10, additive);
                                10: nmfmu_plca_normalize / nmfmu_plca_z / nmfmu_plca3 take alpha as double (an argument changed its
                                   type: not additive).  The Dirichlet prior adds fp32(alpha - 1) with the subtraction in double,
                                   as the reference's in-place add does; fp32(alpha) - 1.f was off by 4.7e-5 relative at
@@ -324,6 +326,26 @@ int nmfmu_mu_apply(const nmfmu_step* st, const float* num, const float* den, int
  * l1 / l2 / gamma come from *st.  Refreshes owner's bf16 images and column sums like nmfmu_mu_apply. */
 int nmfmu_trainer_apply(const nmfmu_step* st, const float* num, const float* den, int nslab, const float* kl_den,
                         float ortho, float* grad, void* stream);
+
+/* ARD-NMF (Tan & Fevotte 2013; torchnmf_amd/ard.py, NMF.fit_ard): column k of W and column k of H share a scale lambda_k,
+ * the update's denominator carries the PER-COMPONENT penalty pen[k] = phi / lambda_k, and lambda follows the factors.
+ * nmfmu_ard_apply: nmfmu_mu_apply(st, NULL, NULL, 0, kl_den) -- st->slab_* with st->nsplit slabs, the same sums in the same
+ * order, the same images, column sums and status bit -- with pen[st->r_pad] (device) in place of st->l1 / st->l2:
+ *   prior NMFMU_ARD_L1 (exponential prior, f(x) = sum x):      pos += pen[r];
+ *   prior NMFMU_ARD_L2 (half-normal prior, f(x) = 1/2 sum x^2): pos += pen[r] * f;       f *= (neg / pos) ** st->gamma
+ * A pen entry of 0 leaves the bits of the unpenalised update; with pen == p everywhere the result is nmfmu_mu_apply's with
+ * st->l1 = p (st->l2 = p), bit for bit.  Also leaves norm[r] = f(owner[:, r]) for r < r_pad (0 in the padding), a
+ * deterministic two-stage sum: 'l1' it is the column sum (norm_part is not touched and may be NULL), 'l2' the per-stripe
+ * partials go to norm_part (nmfmu_colsum_part_bytes floats' worth, like colsum_part).
+ * nmfmu_ard_relevance: one small launch after the two half-steps.  For k < rank:
+ *   lambda = ((norm_w[k] + norm_h[k]) + b) / c;  pen[k] = phi / lambda;  delta[0] = max_k |lambda - lam[k]| / lam[k];  lam[k] = lambda
+ * and lam[k] = pen[k] = 0 for rank <= k < r_pad.  b, c, phi > 0; all pointers device memory. */
+#define NMFMU_ARD_L1 1
+#define NMFMU_ARD_L2 2
+int nmfmu_ard_apply(const nmfmu_step* st, const float* kl_den, const float* pen, int prior, float* norm_part, float* norm,
+                    void* stream);
+int nmfmu_ard_relevance(const float* norm_w, const float* norm_h, int rank, int r_pad, float b, float c, float phi, float* lam,
+                        float* pen, float* delta, void* stream);
 
 /* trainer.BetaMu on a CHAIN of NMF layers (nn.Sequential, tests/test_trainer.py:10-32): the matrix products of the
  * forward / backward passes are nmfmu_reconstruct calls; these are the two pieces in between.

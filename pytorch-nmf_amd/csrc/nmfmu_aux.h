@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+struct nmfmu_step;   // include/nmfmu.h
+
 namespace nmfmu {
 
 struct ApplyArgs {
@@ -91,6 +93,16 @@ int64_t conv_plca_backward_ws_floats(int batch, int channels, int rank, int ndim
 int launch_conv_plca_backward(const float* G, const float* W, const float* H, const float* Z, int batch, int channels, int rank,
                               int ndim, const int32_t* lh, const int32_t* taps, float* grad_h, float* grad_w, float* grad_z,
                               float* ws, hipStream_t s);
+// nmfmu_ard.hip: the apply stage with a per-component penalty (ARD-NMF) and its relevance update.  ApplyArgs as for
+// launch_apply (l1 / l2 / the trainer fields are not read); pen: [r_pad]; l2_prior: pos += pen[r] * f instead of pos += pen[r];
+// norm_part: [rows_pad / 16][r_pad] (worst case; the 'l2' prior only), norm: [r_pad]
+int launch_ard_apply(int r_pad, const ApplyArgs& a, bool x3, const float* pen, bool l2_prior, float* norm_part, float* norm,
+                     hipStream_t s);
+// the apply stage's side of the one-image stages (nmfmu_capi.hip: apply_image_rule): NMFMU_OK or the refusal; *writes_p2: the
+// owner's transposed images are written
+int apply_writes_p2(const nmfmu_step* st, bool* writes_p2);
+int launch_ard_relevance(const float* norm_w, const float* norm_h, int rank, int r_pad, float b, float c, float phi, float* lam,
+                         float* pen, float* delta, hipStream_t s);
 int launch_probe_mfma(const uint16_t* a, const uint16_t* b, float* d, hipStream_t s);
 int launch_probe_lds_dma(const uint32_t* src, uint32_t* dst, int n_dwords, hipStream_t s);
 int launch_ubench_mfma_hbm(const void* operands, size_t operand_bytes, int f16, const void* stream_src, int kib_per_tile,

@@ -243,6 +243,9 @@ struct Timer {
 
 }  // namespace
 
+// (nmfmu_aux.h) apply_image_rule for the apply stages that live in other units (nmfmu_ard.hip)
+int nmfmu::apply_writes_p2(const nmfmu_step* st, bool* writes_p2) { return apply_image_rule(st, writes_p2); }
+
 extern "C" {
 
 int nmfmu_abi_version(void) { return NMFMU_ABI_VERSION; }

@@ -29,6 +29,7 @@ STAGE_DMA_SP128_RB0 = 6     # as STAGE_DMA_SP128 with the kernel's whole ratio s
                             # other arm of an A/B against the shipped placement, bit-identical results
 BETA_KL, BETA_EUC, BETA_IS, BETA_GEN = 0, 1, 2, 3
 KERNEL_FUSED, KERNEL_PP, KERNEL_SP = 0, 1, 2
+ARD_PRIORS = {'l1': 1, 'l2': 2}      # NMFMU_ARD_L1 / NMFMU_ARD_L2
 
 PRECISIONS = {'bf16': PREC_BF16, 'bf16x3': PREC_BF16X3, 'f16': PREC_F16, 'f16x': PREC_F16X, 'f16r': PREC_F16R}
 
@@ -106,6 +107,9 @@ SIGNATURES = {
     'nmfmu_mu_apply': (C.c_int, [C.POINTER(Step), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     'nmfmu_trainer_apply': (C.c_int, [C.POINTER(Step), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float,
                                       C.c_void_p, C.c_void_p]),
+    'nmfmu_ard_apply': (C.c_int, [C.POINTER(Step), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'nmfmu_ard_relevance': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]),
     'nmfmu_loss_part_count': (C.c_int, [C.c_int, C.c_int, C.c_int]),
     'nmfmu_loss': (C.c_int, [C.POINTER(Step), C.c_void_p, C.c_void_p, C.c_void_p]),
     'nmfmu_riding_loss_supported': (C.c_int, [C.POINTER(Step)]),

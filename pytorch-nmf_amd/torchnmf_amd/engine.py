@@ -164,6 +164,16 @@ class HipBackend:
                                             self.stream()), 'nmfmu_mu_apply')
         st.owner.nparts = self.lib.nmfmu_pack_nparts(st.owner.rows_pad)
 
+    # -- ARD-NMF (ard.ArdMU): the apply stage with a per-component penalty, and the relevance update
+    def ard_apply(self, st, kl_den, pen, prior: str, norm_part, norm):
+        _capi.check(self.lib.nmfmu_ard_apply(C.byref(st.struct), _ptr(kl_den), _ptr(pen), _capi.ARD_PRIORS[prior],
+                                             _ptr(norm_part), _ptr(norm), self.stream()), 'nmfmu_ard_apply')
+        st.owner.nparts = self.lib.nmfmu_pack_nparts(st.owner.rows_pad)
+
+    def ard_relevance(self, norm_w, norm_h, rank, r_pad, b, c, phi, lam, pen, delta):
+        _capi.check(self.lib.nmfmu_ard_relevance(_ptr(norm_w), _ptr(norm_h), rank, r_pad, float(b), float(c), float(phi),
+                                                 _ptr(lam), _ptr(pen), _ptr(delta), self.stream()), 'nmfmu_ard_relevance')
+
     def trainer_apply(self, st, kl_den, ortho, grad):
         _capi.check(self.lib.nmfmu_trainer_apply(C.byref(st.struct), None, None, 0, _ptr(kl_den), float(ortho),
                                                  _ptr(grad), self.stream()), 'nmfmu_trainer_apply')

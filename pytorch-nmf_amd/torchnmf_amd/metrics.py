@@ -48,7 +48,7 @@ from .separation import separate
 
 __all__ = ['kl_div', 'euclidean', 'is_div', 'beta_div', 'sparseness', 'SparseTarget', 'sparse_beta_div', 'score_pairs',
            'topk_scores', 'rank_scores', 'ranking_metrics', 'fold_in', 'fold_in_cd', 'WeightedTarget', 'weighted_beta_div',
-           'batched_beta_div', 'separate']
+           'batched_beta_div', 'separate', 'ard_objective']
 
 
 def _beta_div_value(input: Tensor, target: Tensor, beta: float) -> Tensor:
@@ -110,6 +110,38 @@ def euclidean(input: Tensor, target: Tensor) -> Tensor:
 def is_div(input: Tensor, target: Tensor) -> Tensor:
     """Itakura-Saito divergence = beta_div(beta=0) (metrics.py:42-57)."""
     return beta_div(input, target, 0)
+
+
+def ard_objective(H: Tensor, W: Tensor, V: Tensor, lam: Tensor, beta: float, prior: str, phi: float, a: float,
+                  b: float) -> Tensor:
+    """The objective ``NMF.fit_ard`` minimises (``ard.py``), 0-dim float64 on the inputs' device, not differentiable::
+
+        beta_div(H W^T, V) / phi + sum_k [ (f(W[:, k]) + f(H[:, k]) + b) / lam_k + c log lam_k ]
+
+    ``f = ||.||_1``, ``c = N + C + a + 1`` (prior 'l1'); ``f = 1/2 ||.||^2``, ``c = (N + C) / 2 + a + 1`` ('l2').  Plain
+    float64 torch arithmetic with the reference's eps conventions (metrics.py:22, 56-57, 85-88): a check of the fit, not a
+    part of it -- it forms the ``N x C`` product."""
+    from .ard import ard_c, check_prior
+    from .constants import eps
+    check_prior(prior, a)
+    beta = float(beta)
+    with torch.no_grad():
+        H64, W64, y = H.detach().double(), W.detach().double(), V.detach().double()
+        x = H64 @ W64.t()
+        if beta == 2:
+            div = 0.5 * ((x - y) ** 2).sum()
+        elif beta == 1:
+            div = (y * ((y + eps).log() - (x + eps).log())).sum() - y.sum() + x.sum()
+        elif beta == 0:
+            q = (y + eps) / (x + eps)
+            div = (q - q.log()).sum() - y.numel()
+        else:
+            xe, yf = x + eps, (y + eps if beta < 0 else y)
+            div = (yf.pow(beta).sum() + (beta - 1) * xe.pow(beta).sum() - beta * (yf * xe.pow(beta - 1)).sum()) / (beta * (beta - 1))
+        f = (lambda t: t.sum(0)) if prior == 'l1' else (lambda t: 0.5 * (t * t).sum(0))
+        lam64 = lam.detach().double()
+        c = ard_c(H.shape[0], W.shape[0], float(a), prior)
+        return div / float(phi) + ((f(W64) + f(H64) + float(b)) / lam64 + c * lam64.log()).sum()
 
 
 def sparseness(x: Tensor) -> Tensor:

@@ -235,6 +235,10 @@ class BaseComponent(nn.Module):
     def _make_engine(self, V, beta, l1, l2, precision, group, allreduce=None):
         raise NotImplementedError
 
+    def fit_ard(self, V: Tensor, *args, **kwargs) -> int:
+        """ARD-NMF (``NMF.fit_ard``) is not implemented for the convolutive models."""
+        raise NotImplementedError(f'fit_ard is implemented for NMF only, not {type(self).__name__}')
+
     def _projected_half_step(self, p, recon, V, beta: float, l1: float, stepsize: float) -> float:
         """One sparseness-constrained half-step on the factor ``p`` (nmf.py:494-520 / 545-572): the gradient of
         ``beta_div(recon(p), V, beta)`` through the autograd kernels, then up to 10 tries of gradient step, projection of
@@ -748,6 +752,142 @@ class NMF(BaseComponent):
         H.data.copy_(bm.H.data[best])
         self.last_precision = bm.last_precision
         return n_iter, losses, best
+
+    @torch.no_grad()
+    def fit_ard(self, V: Tensor, beta: float = 1, prior: str = 'l1', phi: float = 1.0, a: float = 5.0,
+                b: Optional[float] = None, tol: float = 1e-5, max_iter: int = 1000, verbose: bool = False, *,
+                precision: Optional[str] = None) -> int:
+        """Fit with automatic relevance determination (Tan & Fevotte, IEEE TPAMI 2013): start from a generous rank, fit ONCE,
+        and let the update shrink the components the data does not need -- the one-fit answer to "which rank?" (the other one
+        is ``model_selection.cross_validate``, one batched fit per candidate).
+
+        Model: column ``k`` of ``W`` and column ``k`` of ``H`` share a scale ``lambda_k`` with an inverse-gamma prior
+        (shape ``a``, scale ``b``); their entries are exponential (``prior='l1'``) or half-normal (``prior='l2'``) with that
+        scale.  The fit minimises ::
+
+            D_beta(V | H W^T) / phi + sum_k [ (f(W[:, k]) + f(H[:, k]) + b) / lambda_k + c log lambda_k ]
+
+        with ``f = ||.||_1``, ``c = N + C + a + 1`` ('l1') or ``f = 1/2 ||.||^2``, ``c = (N + C) / 2 + a + 1`` ('l2'), by the
+        multiplicative update of ``fit`` with the per-component penalty ``phi / lambda_k`` in its denominator (``ard.ArdMU``;
+        W half-step, H half-step, then ``lambda_k = (f(W[:, k]) + f(H[:, k]) + b) / c``), which never increases it.
+
+        ``phi`` is the DISPERSION of the noise model (the variance for beta = 2; for beta = 1 and 0 the scale of the
+        Poisson / gamma noise) and must match the data's scale and noise: it weighs the fit against the prior, and the number
+        of components that survive depends on it -- too small and nothing is pruned, too large and real components go too.
+        This method does not estimate it.  ``a`` must be > 2 ('l1') or > 1 ('l2'); ``b`` defaults to the moment match
+        ``mean(V) = R E[w] E[h]`` (``ard.default_b``).
+
+        Stop rule: every 10th iteration, stop when that iteration's ``max_k |lambda_k - previous lambda_k| / previous
+        lambda_k < tol``.  Returns the number of iterations.  Afterwards ``last_relevance`` holds lambda (fp32 ``[R]``),
+        ``last_relative_relevance`` holds ``(lambda - B) / B`` with the floor ``B = b / c`` (about 0 for a pruned component)
+        and ``last_precision`` names the mode that ran.  No component is removed: see ``effective_rank`` and ``prune``.
+
+        Dense targets, ``NMF`` only, rank <= 256 on the fused kernels (``precision`` as in ``fit``), not sharded.  A frozen
+        factor (``requires_grad=False``) is not updated; its norm still enters lambda."""
+        from .ard import ArdMU, check_prior, default_b
+        if V.is_sparse:
+            raise NotImplementedError('fit_ard: sparse targets are not implemented (dense targets only)')
+        check_prior(prior, a)
+        if not float(phi) > 0:
+            raise ValueError(f'phi (the dispersion) must be > 0, got {phi!r}')
+        if b is not None and not float(b) > 0:
+            raise ValueError(f'b must be > 0, got {b!r}')
+        W, H = self.W, self.H
+        assert W is not None and H is not None
+        R = W.shape[1]
+        if R > 256:
+            raise NotImplementedError(f'fit_ard: rank {R} > 256, the limit of the fused kernels')
+        _require_device(V, 'fit_ard')
+        _require_device(W, 'fit_ard')
+        _require_device(H, 'fit_ard')
+        if W.dtype != torch.float32 or H.dtype != torch.float32:      # fp32 working copies, as in fit
+            if not (W.dtype.is_floating_point and H.dtype.is_floating_point):
+                raise NotImplementedError(f'factors must be floating point; got W {W.dtype}, H {H.dtype}')
+            keep = (W.data, H.data)
+            W.data, H.data = W.data.float().contiguous(), H.data.float().contiguous()
+            try:
+                return self.fit_ard(V, beta, prior, phi, a, b, tol, max_iter, verbose, precision=precision)
+            finally:
+                w32, h32 = W.data, H.data
+                W.data, H.data = keep
+                W.data.copy_(w32)
+                H.data.copy_(h32)
+        if precision is None:
+            precision = os.environ.get('TORCHNMF_AMD_PRECISION', 'auto')
+        beta = float(beta)
+        V = V.detach()
+        if V.dtype != torch.float32:
+            V = V.float()
+        assert V.dim() == 2 and V.shape == (H.shape[0], W.shape[0]), \
+            f'V must be {(H.shape[0], W.shape[0])}, got {tuple(V.shape)}'
+        for p in (W, H):
+            if not p.data.is_contiguous():
+                p.data = p.data.contiguous()
+        if b is None:
+            v_mean = float(V.mean(dtype=torch.float64))
+            # (a mean that is not positive -- negative entries, NaN, all zeros: the target checks below say what is wrong)
+            b = default_b(v_mean, R, float(a), prior) if v_mean > 0 else 1.0
+        eng = ArdMU(V, W.data, H.data, beta, prior, phi, a, b, precision, update_W=W.requires_grad,
+                    update_H=H.requires_grad)
+        self.last_precision = eng.precision_name
+        has_bad, has_zero = eng.target_flags()
+        assert not has_bad, "Target should be non-negative."
+        if has_zero and beta <= 0:
+            raise ValueError("When beta <= 0 and V contains zeros, the training process may diverge. "
+                             "Please add small values to V, or use a positive beta value.")
+        pbar = None
+        if verbose:
+            from tqdm import tqdm
+            pbar = tqdm(total=max_iter)
+        n_iter = -1
+        try:
+            for n_iter in range(max_iter):
+                if W.requires_grad:
+                    eng.w_step()
+                if H.requires_grad:
+                    eng.h_step()
+                eng.relevance_step()
+                if n_iter % 10 == 9:
+                    delta = float(eng.delta)          # the loop's one host sync
+                    if pbar is not None:
+                        pbar.set_postfix(delta=delta)
+                        pbar.update(10)
+                    if delta < tol:
+                        break
+            if eng.left_f16_range():
+                import warnings
+                warnings.warn("torchnmf_amd: a factor grew beyond fp16's range (65504) during the fit; its fp16 operand "
+                              "image was clamped and the updates no longer follow the model.  Re-run with "
+                              "precision='bf16x3' (or rescale V).")
+        finally:
+            if pbar is not None:
+                pbar.close()
+        self.last_relevance = eng.lam.clone()
+        self.last_relative_relevance = eng.relative_relevance()
+        return n_iter + 1
+
+    def _relative_relevance(self) -> Tensor:
+        rel = getattr(self, 'last_relative_relevance', None)
+        if rel is None or rel.numel() != self.W.shape[1]:
+            raise RuntimeError('no relevance to judge by: call fit_ard first')
+        return rel
+
+    def effective_rank(self, rel_tol: float = 1e-2) -> int:
+        """Number of components whose relative relevance after ``fit_ard`` exceeds ``rel_tol``."""
+        return int((self._relative_relevance() > rel_tol).sum())
+
+    def prune(self, rel_tol: float = 1e-2) -> 'NMF':
+        """A new ``NMF`` holding only the components that survived ``fit_ard`` (relative relevance > ``rel_tol``), in their
+        original order, on this module's device and in its dtype; this module is not modified."""
+        keep = (self._relative_relevance() > rel_tol).nonzero().flatten().to(self.W.device)
+        if keep.numel() == 0:
+            raise RuntimeError(f'prune: no component has a relative relevance above {rel_tol:g}')
+        W, H = self.W.data.index_select(1, keep), self.H.data.index_select(1, keep)
+        out = NMF(W=W.float().cpu(), H=H.float().cpu(), trainable_W=self.W.requires_grad, trainable_H=self.H.requires_grad)
+        out = out.to(device=self.W.device, dtype=self.W.dtype)
+        out.W.data.copy_(W)
+        out.H.data.copy_(H)
+        return out
 
     def predict(self, rows: Tensor, cols: Tensor) -> Tensor:
         """The model's value at (row, column) pairs, fp32 ``[n]``, without the ``N x C`` reconstruction
