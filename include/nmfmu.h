@@ -93,6 +93,9 @@ extern "C" {
                                   additive);
                                   nmfmu_ard_apply / nmfmu_ard_relevance (NMF.fit_ard: the apply stage with a per-component
                                   penalty and the relevance update of ARD-NMF; added at ABI 10, additive);
+                                  nmfmu_ntf_terms / nmfmu_ntf_step / nmfmu_ntf_loss / nmfmu_ntf_ws / nmfmu_ntf_nsplit /
+                                  nmfmu_ntf_loss_parts (ntf.NTF: non-negative CP factorisation of a 3-way tensor walked in
+                                  place, Khatri-Rao rows formed in LDS; added at ABI 10, additive);
                                10: nmfmu_plca_normalize / nmfmu_plca_z / nmfmu_plca3 take alpha as double (an argument changed its
                                   type: not additive).  The Dirichlet prior adds fp32(alpha - 1) with the subtraction in double,
                                   as the reference's in-place add does; fp32(alpha) - 1.f was off by 4.7e-5 relative at
@@ -960,6 +963,38 @@ int nmfmu_bwmu_loss(const float* V, int64_t v_batch_stride, const float* M, int6
                     const double* v_term, const int32_t* active, double* part, double* out, void* stream);
 int nmfmu_bwmu_v_term(const float* V, int64_t v_batch_stride, const float* M, int64_t m_batch_stride, const int32_t* m_index,
                       int64_t ld, int batch, int n, int c, float beta, double* out, void* stream);
+
+/* ---- non-negative CP factorisation of a 3-way tensor (ntf.NTF; additive entries) ----------------------------------------------
+ * V[i][j][k] ~ sum_r A[i][r] B[j][r] C[k][r], L = sum m d_beta(v | y).  V: contiguous fp32 [I][J][K]; M: NULL (unweighted, m = 1)
+ * or dense fp32 weights of V's shape, m >= 0; A [I][rank], B [J][rank], C [K][rank]: contiguous fp32 masters.  A half-step of
+ * `mode` updates one factor (the owner) over the flat contraction axis (a, b), a-major, of the other two modes:
+ *   mode 0: owner A, (a, b) = (j, k), (pa, pb) = (B, C);  mode 1: owner B, (i, k), (A, C);  mode 2: owner C, (i, j), (A, B)
+ *   p[r] = fl32(pa[a][r] pb[b][r]) (one rounding),  y = sum_r owner[o][r] p[r] (r ascending),
+ *   num[o][r] = sum_(a,b) (m g_neg(v, y)) p[r],  den[o][r] = sum_(a,b) (m g_pos(y)) p[r]
+ * with the seeds, the selection of m == 0 (V may hold anything there), the tile, the part order and the apply of the
+ * nmfmu_wmu entries.  V and M are walked in place in every mode and the Khatri-Rao rows are formed 32 at a time in LDS:
+ * nothing of the tensor's size and no Khatri-Rao matrix is allocated.  The contraction is cut into parts of whole 32-step
+ * stages: nsplit == 0 takes nmfmu_ntf_nsplit(owner rows, contraction, r_pad) -- 512 workgroups' worth however few row tiles
+ * there are, parts of >= 4 stages, no cap at 64 -- and nsplit > 0 asks for that many.  ws: nmfmu_ntf_ws(...) floats,
+ * [part][num | den][owner rows][r_pad], plain stores, added in part order by a second kernel: a repeated call is bitwise
+ * identical whatever ws held.
+ *   nmfmu_ntf_terms      : num, den [owner rows][r_pad]; every element is written, the padded columns with 0.
+ *   nmfmu_ntf_step       : the same terms, then nmf.py:78-92 in place on the owner.  The owner aliases neither pa nor pb.
+ *   nmfmu_ntf_loss       : *out = sum m (the term of metrics.beta_div), summed as nmfmu_wmu_loss does over the mode-0 walk;
+ *                          v_term: sum m (the terms of v alone), float64, from the caller.  part: nmfmu_ntf_loss_parts doubles.
+ * Null pointers (M excepted), I, J, K, rank <= 0, mode not 0 / 1 / 2, r_pad != nmfmu_pad_rank(rank), nsplit < 0, an aliased
+ * owner (step): NMFMU_ERR_ARG; rank > 256, a contraction of more than 2^30 steps or a forced nsplit that gives more than
+ * 65535 parts: NMFMU_ERR_UNSUPPORTED -- both before any device work. */
+int nmfmu_ntf_nsplit(int rows, int contraction, int r_pad);
+int64_t nmfmu_ntf_ws(int rows, int contraction, int r_pad, int nsplit);
+int nmfmu_ntf_terms(const float* V, const float* M, int I, int J, int K, int mode, const float* owner, const float* pa,
+                    const float* pb, int rank, int r_pad, float beta, int nsplit, float* ws, float* num, float* den,
+                    void* stream);
+int nmfmu_ntf_step(const float* V, const float* M, int I, int J, int K, int mode, float* owner, const float* pa, const float* pb,
+                   int rank, int r_pad, float beta, float l1, float l2, float gamma, int nsplit, float* ws, void* stream);
+int nmfmu_ntf_loss_parts(int I, int J, int K);
+int nmfmu_ntf_loss(const float* V, const float* M, int I, int J, int K, const float* A, const float* B, const float* C, int rank,
+                   float beta, double v_term, double* part, double* out, void* stream);
 
 /* ---- PLCA's EM update (plca.py:248-290) -----------------------------------------------------------------------------
  * With G = Vn / (H diag(Z) W^T + eps) the factor "gradients" are (G^T H) * Z, (G W) * Z and Z.grad[r] = sum W * (G^T H);

@@ -10,4 +10,4 @@ The beta-divergence MU hot path of yoyololicon/pytorch-NMF (dense and sparse-COO
 name = 'torchnmf_amd'
 __version__ = '0.1.0'
 
-from . import constants, metrics, nmf, plca, trainer  # noqa: E402,F401
+from . import constants, metrics, nmf, ntf, plca, trainer  # noqa: E402,F401

@@ -187,6 +187,15 @@ SIGNATURES = {
     'nmfmu_wmu_loss_parts': (C.c_int, [C.c_int, C.c_int]),
     'nmfmu_wmu_loss': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float,
                                  C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'nmfmu_ntf_nsplit': (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    'nmfmu_ntf_ws': (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    'nmfmu_ntf_terms': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'nmfmu_ntf_step': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
+    'nmfmu_ntf_loss_parts': (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    'nmfmu_ntf_loss': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                 C.c_float, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     'nmfmu_bmu_nsplit': (C.c_int, [C.c_int, C.c_int, C.c_int]),
     'nmfmu_bmu_ws': (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     'nmfmu_bmu_terms': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,

@@ -1,0 +1,272 @@
+"""Non-negative tensor factorisation: the CP / PARAFAC model of a 3-way tensor, ``NTF(V.shape, rank).fit(V, weights=M)``.
+
+``V[i, j, k] ~ sum_r A[i, r] B[j, r] C[k, r]`` fitted by the beta-divergence multiplicative update of ``NMF.fit`` (nmf.py:61-92),
+``L = sum m d_beta(v | y)`` with optional dense weights ``m >= 0`` of ``V``'s shape (0 marks a missing entry: ``V`` may hold
+anything there).  One half-step is one ``nmfmu_ntf_step`` call on the fp32 masters: the fused exact-fp32 MFMA kernel of
+csrc/nmfmu_ntf.hip walks the three unfoldings of the row-major tensor in place and forms the Khatri-Rao rows 32 at a time in
+LDS -- nothing of ``V``'s size and no Khatri-Rao matrix is allocated beyond ``V`` and ``M`` themselves.
+"""
+from __future__ import annotations
+
+from typing import Optional, Sequence
+
+import torch
+from torch import Tensor, nn
+
+from . import _capi
+from .constants import eps
+from .engine import mu_gamma
+from .nmf import _require_device, _sqrt2
+from .wmu import check_weights
+
+__all__ = ['NTF', 'NtfTarget', 'ntf_terms', 'ntf_loss']
+
+MAX_RANK = 256
+MAX_CONTRACTION = 1 << 30      # csrc/nmfmu_ntf.hip: the flat contraction steps of a mode are ints
+_CHUNK = 1 << 22      # elements per slice of the one-time scans of the target: their temporaries stay small beside V
+
+
+def _check_shape(shape, rank: int) -> None:
+    """The limits of the C entries, refused here before anything is scanned, allocated or launched."""
+    if rank > MAX_RANK:
+        raise NotImplementedError(f'NTF: rank {rank} > {MAX_RANK}, the limit of the exact-fp32 kernels')
+    I, J, K = shape
+    if max(J * K, I * K, I * J) > MAX_CONTRACTION:
+        raise NotImplementedError(f'NTF: a mode of {tuple(shape)} contracts over more than 2^30 entries, the limit of the kernels')
+
+
+def _stream() -> int:
+    return torch.cuda.current_stream().cuda_stream
+
+
+class NtfTarget:
+    """A dense 3-way target with optional weights, prepared once: contiguous fp32 ``V`` (and ``M``), the two flags of
+    nmf.py:329-336 (over the weighted entries only when weights are given) and the terms of the loss that hold ``v`` alone
+    per beta.  The scans run over slices of the flat tensor, so nothing of ``V``'s size is allocated.  ``checked``: the
+    weights already went through ``wmu.check_weights`` (``fit`` validates them before it asks for the device)."""
+
+    def __init__(self, V: Tensor, weights=None, checked: bool = False):
+        if not isinstance(V, Tensor) or V.is_sparse or V.dim() != 3:
+            raise ValueError('an NTF target is a dense 3-D tensor')
+        self.M = weights if weights is None or checked else check_weights(V, weights)
+        self.V = V.detach().float().contiguous()
+        self.shape, self.device = tuple(V.shape), V.device
+        self._v_term = {}
+        bad = torch.zeros((), dtype=torch.bool, device=self.device)
+        zero = torch.zeros((), dtype=torch.bool, device=self.device)
+        for v, m in self._slices():
+            if m is not None:
+                v = torch.where(m > 0, v, torch.ones((), device=self.device))
+            bad |= ~(v >= 0).all()                                     # negative or NaN where it counts
+            zero |= (v == 0).any()
+        self.bad, self.has_zero = bool(bad.item()), bool(zero.item())
+
+    def _slices(self):
+        v, m = self.V.view(-1), None if self.M is None else self.M.view(-1)
+        for at in range(0, v.numel(), _CHUNK):
+            yield v[at:at + _CHUNK], None if m is None else m[at:at + _CHUNK]
+
+    def v_term(self, beta: float) -> float:
+        """``sum m * (the terms of metrics.beta_div that hold v alone)`` (metrics.py:22, 39, 57, 85-96) in float64 -- what
+        ``nmfmu_ntf_loss`` takes as ``v_term``.  Once per (target, beta); a Python float."""
+        if beta not in self._v_term:
+            tot = torch.zeros((), dtype=torch.float64, device=self.device)
+            for v, m in self._slices() if beta != 2.0 else ():
+                vd = (v if m is None else torch.where(m > 0, v, torch.ones((), device=self.device))).double()
+                if beta == 1.0:
+                    t = vd * (vd + eps).log() - vd
+                elif beta == 0.0:
+                    t = -(vd + eps).log() - 1.0
+                else:
+                    t = (vd + eps if beta < 0 else vd).pow(beta)
+                tot += (t if m is None else m.double() * t).sum()
+            self._v_term[beta] = float(tot.item())
+        return self._v_term[beta]
+
+
+def _ntf_call(T: NtfTarget, factors: Sequence[Tensor], mode: int, beta: float, step=None, nsplit: int = 0, _fill=None,
+              _ws=None):
+    """``nmfmu_ntf_terms`` (``step`` None: returns (num, den), fp32 ``[dim_mode, r_pad]``) or ``nmfmu_ntf_step`` (``step`` =
+    (l1, l2, gamma): ``factors[mode]`` updated in place).  ``factors``: three contiguous fp32 ``[dim_n, R]``.  Enqueued only.
+    ``_fill``: tests pre-fill the outputs and the workspace with it."""
+    lib = _capi.load()
+    I, J, K = T.shape
+    owner = factors[mode]
+    pa, pb = (f for n, f in enumerate(factors) if n != mode)
+    rows, R = owner.shape
+    assert tuple(f.shape for f in factors) == ((I, R), (J, R), (K, R))
+    r_pad = lib.nmfmu_pad_rank(R)
+    contraction = I * J * K // rows
+    n_float = lib.nmfmu_ntf_ws(rows, contraction, r_pad, nsplit)
+    ws = _ws if _ws is not None else torch.empty(max(n_float, 1), dtype=torch.float32, device=T.device)
+    assert ws.numel() >= n_float
+    if _fill is not None:
+        ws.fill_(_fill)
+    head = (T.V.data_ptr(), None if T.M is None else T.M.data_ptr(), I, J, K, mode, owner.data_ptr(), pa.data_ptr(),
+            pb.data_ptr(), R, r_pad, beta)
+    if step is not None:
+        l1, l2, gamma = step
+        _capi.check(lib.nmfmu_ntf_step(*head, l1, l2, gamma, nsplit, ws.data_ptr(), _stream()), 'nmfmu_ntf_step')
+        return None
+    num = torch.empty(rows, r_pad, dtype=torch.float32, device=T.device)
+    den = torch.empty(rows, r_pad, dtype=torch.float32, device=T.device)
+    if _fill is not None:
+        num.fill_(_fill)
+        den.fill_(_fill)
+    _capi.check(lib.nmfmu_ntf_terms(*head, nsplit, ws.data_ptr(), num.data_ptr(), den.data_ptr(), _stream()),
+                'nmfmu_ntf_terms')
+    return num, den
+
+
+def _ntf_loss(T: NtfTarget, factors: Sequence[Tensor], beta: float, part=None, out=None) -> Tensor:
+    """The loss as a 1-element float64 device tensor.  Enqueued only (the terms of v alone are cached on the target)."""
+    lib = _capi.load()
+    I, J, K = T.shape
+    A, B, Cf = factors
+    if part is None:
+        part = torch.empty(lib.nmfmu_ntf_loss_parts(I, J, K), dtype=torch.float64, device=T.device)
+    if out is None:
+        out = torch.empty(1, dtype=torch.float64, device=T.device)
+    _capi.check(lib.nmfmu_ntf_loss(T.V.data_ptr(), None if T.M is None else T.M.data_ptr(), I, J, K, A.data_ptr(), B.data_ptr(),
+                                   Cf.data_ptr(), A.shape[1], beta, T.v_term(beta), part.data_ptr(), out.data_ptr(), _stream()),
+                'nmfmu_ntf_loss')
+    return out
+
+
+def _prepare(V, weights, factors):
+    """The refusals first (shape limits, the device), then the target's scans and the fp32 factors."""
+    _check_shape(tuple(V.shape), factors[0].shape[1])
+    for t in (V.V if isinstance(V, NtfTarget) else V, *factors):
+        _require_device(t, 'NTF')
+    T = V if isinstance(V, NtfTarget) else NtfTarget(V, weights)
+    return T, [f.detach().float().contiguous() for f in factors]
+
+
+def ntf_terms(V, weights, factors: Sequence[Tensor], mode: int, beta: float, nsplit: int = 0):
+    """``(num, den)`` of the half-step of ``mode`` (0, 1 or 2), fp32 ``[dim_mode, r_pad]`` with zeros in the padded rank
+    columns; ``den - num`` is the gradient of the loss with respect to ``factors[mode]``.  ``V``: a dense ``[I, J, K]`` device
+    tensor with ``weights`` of its shape or None, or an ``NtfTarget`` prepared once."""
+    T, fs = _prepare(V, weights, factors)
+    return _ntf_call(T, fs, int(mode), float(beta), nsplit=nsplit)
+
+
+def ntf_loss(V, weights, factors: Sequence[Tensor], beta: float) -> Tensor:
+    """``sum weights * d_beta(V | reconstruction)`` with the reference's ``beta_div`` terms, without the reconstruction: a
+    0-dim float64 device tensor.  Arguments as for ``ntf_terms``."""
+    T, fs = _prepare(V, weights, factors)
+    return _ntf_loss(T, fs, float(beta))[0]
+
+
+class NTF(nn.Module):
+    """Non-negative CP factorisation ``V (I, J, K) ~ sum_r A[:, r] x B[:, r] x C[:, r]``.
+
+    ``factors`` is a ``ParameterList`` of three ``[dim_n, rank]`` tensors, drawn from ``|N(0, 1)|`` like ``NMF``'s or given;
+    ``trainable[n]`` False freezes factor ``n``.  ``fit`` is the multiplicative update on the HIP kernels; ``forward`` is a
+    plain ``torch.einsum`` and there is no autograd support for the fit's kernels."""
+
+    def __init__(self, Vshape=None, rank: Optional[int] = None, factors=None, trainable=(True, True, True)):
+        super().__init__()
+        if factors is not None:
+            factors = list(factors)
+            assert len(factors) == 3 and all(isinstance(f, Tensor) and f.dim() == 2 for f in factors), \
+                'factors: three [dim_n, rank] tensors'
+            assert len({f.shape[1] for f in factors}) == 1, 'the factors must share their rank'
+            assert all(bool(torch.all(f >= 0.)) for f in factors), 'the factors should be non-negative.'
+            assert rank is None or rank == factors[0].shape[1], 'rank does not match the factors'
+            assert Vshape is None or tuple(Vshape) == tuple(f.shape[0] for f in factors), 'Vshape does not match the factors'
+            data = [f.detach().clone() for f in factors]
+        else:
+            shape = tuple(Vshape)
+            if len(shape) != 3:
+                raise NotImplementedError(f'NTF factorises tensors of order 3, got order {len(shape)}')
+            assert rank is not None and rank > 0, 'NTF needs a rank (or the factors)'
+            data = [torch.randn(d, rank).abs() for d in shape]
+        self.factors = nn.ParameterList([nn.Parameter(d, requires_grad=bool(t)) for d, t in zip(data, trainable)])
+        self.rank = self.factors[0].shape[1]
+
+    def forward(self) -> Tensor:
+        """The reconstruction ``[I, J, K]`` (a ``torch.einsum`` on the factors; not the hot path, not differentiable through
+        the HIP kernels -- ``fit`` never calls it)."""
+        A, B, Cf = self.factors
+        return torch.einsum('ir,jr,kr->ijk', A, B, Cf)
+
+    def fit(self, V: Tensor, beta: float = 1, tol: float = 1e-4, max_iter: int = 200, verbose: bool = False, alpha: float = 0,
+            l1_ratio: float = 0, weights=None) -> int:
+        """Fit the trainable factors to ``V`` by multiplicative updates: one iteration updates modes 0, 1, 2 in that order.
+        Loss checkpoints and the stop rule are ``NMF.fit``'s (after iterations 9, 19, ...: stop when
+        ``(previous - loss) / loss_init < tol``); returns the number of iterations.  ``weights``: None, or a dense tensor of
+        ``V``'s shape (bool, integer or floating, >= 0); entries of weight 0 count for nothing whatever ``V`` holds there.
+        ``alpha`` / ``l1_ratio`` regularise as in ``NMF.fit``.  Rank <= 256, exact fp32, device tensors only."""
+        if not isinstance(V, Tensor):
+            raise ValueError(f'NTF.fit takes a dense 3-D tensor, got {type(V).__name__}')
+        if V.is_sparse:
+            raise NotImplementedError("NTF.fit takes a dense tensor; missing entries are given by weights=, and a sparse "
+                                      "matrix is fitted over its stored entries by NMF.fit(..., unstored='missing')")
+        if V.dim() != 3:
+            raise NotImplementedError(f'NTF factorises tensors of order 3, got order {V.dim()}')
+        if tuple(V.shape) != tuple(f.shape[0] for f in self.factors):
+            raise ValueError(f'target {tuple(V.shape)} does not match the factors '
+                             f'{tuple(f.shape[0] for f in self.factors)}')
+        _check_shape(tuple(V.shape), self.rank)
+        if weights is not None:
+            weights = check_weights(V, weights)
+        _require_device(V, 'NTF.fit')
+        for f in self.factors:
+            _require_device(f, 'NTF.fit')
+        if any(f.dtype != torch.float32 for f in self.factors):
+            # fitted on fp32 working copies and stored back in the module's dtype, as NMF.fit does
+            if not all(f.dtype.is_floating_point for f in self.factors):
+                raise NotImplementedError(f'factors must be floating point; got {[f.dtype for f in self.factors]}')
+            keep = [f.data for f in self.factors]
+            for f in self.factors:
+                f.data = f.data.float().contiguous()
+            try:
+                return self.fit(V, beta, tol, max_iter, verbose, alpha, l1_ratio, weights)
+            finally:
+                for f, k in zip(self.factors, keep):
+                    f32, f.data = f.data, k
+                    f.data.copy_(f32)
+        beta = float(beta)
+        step = (float(alpha * l1_ratio), float(alpha * (1 - l1_ratio)), mu_gamma(beta))     # nmf.py:348-349
+        T = NtfTarget(V, weights, checked=True)
+        assert not T.bad, "Target should be non-negative."
+        if T.has_zero and beta <= 0:
+            raise ValueError("When beta <= 0 and V contains zeros, the training process may diverge. "
+                             "Please add small values to V, or use a positive beta value.")
+        for f in self.factors:
+            if not f.data.is_contiguous():
+                f.data = f.data.contiguous()
+        fs = [f.data for f in self.factors]
+        lib, (I, J, K) = _capi.load(), T.shape
+        r_pad = lib.nmfmu_pad_rank(self.rank)
+        ws = torch.empty(max(lib.nmfmu_ntf_ws(d, I * J * K // d, r_pad, 0) for d in T.shape), dtype=torch.float32,
+                         device=T.device)
+        part = torch.empty(lib.nmfmu_ntf_loss_parts(I, J, K), dtype=torch.float64, device=T.device)
+        out = torch.zeros(1, dtype=torch.float64, device=T.device)
+
+        def divergence() -> float:
+            return float(_ntf_loss(T, fs, beta, part, out).item())
+
+        loss_init = previous = _sqrt2(divergence())      # nmf.py:355-363
+        pbar = None
+        if verbose:
+            from tqdm import tqdm
+            pbar = tqdm(total=max_iter)
+        n_iter = -1
+        try:
+            for n_iter in range(max_iter):
+                for mode, f in enumerate(self.factors):
+                    if f.requires_grad:
+                        _ntf_call(T, fs, mode, beta, step=step, _ws=ws)
+                if n_iter % 10 == 9:
+                    loss = _sqrt2(divergence())
+                    if pbar is not None:
+                        pbar.set_postfix(loss=loss)
+                        pbar.update(10)
+                    if (previous - loss) / loss_init < tol:      # nmf.py:402-407
+                        break
+                    previous = loss
+        finally:
+            if pbar is not None:
+                pbar.close()
+        return n_iter + 1
