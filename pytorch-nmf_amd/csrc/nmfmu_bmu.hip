@@ -434,41 +434,30 @@ __global__ void __launch_bounds__(256) bmu_reduce_kernel(const double* __restric
                                                          const int32_t* __restrict__ active, double* __restrict__ out) {
   const int prob = blockIdx.x, tid = threadIdx.x;
   if (active && !active[prob]) return;
-  __shared__ double red[256];
   double s = 0.0;
   for (int i = tid; i < nblk; i += 256) s += part[(size_t)prob * nblk + i];
-  red[tid] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) red[tid] += red[tid + o];
-    __syncthreads();
-  }
-  if (tid == 0) out[prob] = (v_term[prob] + red[0]) * mul;
+  s = block_sum_256(s);
+  if (tid == 0) out[prob] = (v_term[prob] + s) * mul;
 }
 
-// out[problem] = the sum over the problem's entries of the terms of metrics.beta_div that hold v alone (metrics.py:22, 57,
-// 85-96), every term and the sum in double: one workgroup per problem, strided lanes, then a tree -- a pure function of the
-// problem's own entries, whatever the batch around it
+// the terms of metrics.beta_div that hold v alone at one entry (metrics.py:22, 57, 85-96), in double
+__device__ __forceinline__ double bmu_v_term(double v, double beta, int kind) {
+  const double e = (double)kEps;
+  if (kind == NMFMU_BETA_KL) return v * log(v + e) - v;
+  if (kind == NMFMU_BETA_IS) return -log(v + e) - 1.0;
+  return pow(beta < 0.0 ? v + e : v, beta);
+}
+
+// out[problem] = the sum of bmu_v_term over the problem's entries, the sum in double: one workgroup per problem, strided
+// lanes, then a tree -- a pure function of the problem's own entries, whatever the batch around it
 __global__ void __launch_bounds__(256) bmu_v_term_kernel(const float* __restrict__ Vb, int64_t vstride, int64_t ld, int n, int c,
                                                          double beta, int kind, double* __restrict__ out) {
-  __shared__ double red[256];
   const int tid = threadIdx.x;
   const float* V = Vb + (size_t)blockIdx.x * vstride;
-  const double e = (double)kEps;
   double s = 0.0;
-  for (int64_t at = tid; at < (int64_t)n * c; at += 256) {
-    const double v = (double)V[(size_t)(at / c) * ld + at % c];
-    if (kind == NMFMU_BETA_KL) s += v * log(v + e) - v;
-    else if (kind == NMFMU_BETA_IS) s += -log(v + e) - 1.0;
-    else s += pow(beta < 0.0 ? v + e : v, beta);
-  }
-  red[tid] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) red[tid] += red[tid + o];
-    __syncthreads();
-  }
-  if (tid == 0) out[blockIdx.x] = kind == NMFMU_BETA_EUC ? 0.0 : red[0];
+  for (int64_t at = tid; at < (int64_t)n * c; at += 256) s += bmu_v_term((double)V[(size_t)(at / c) * ld + at % c], beta, kind);
+  s = block_sum_256(s);
+  if (tid == 0) out[blockIdx.x] = kind == NMFMU_BETA_EUC ? 0.0 : s;
 }
 
 // bmu_v_term_kernel over the weighted entries: m times the term, both in double; an entry with m == 0 is selected away
@@ -476,30 +465,17 @@ __global__ void __launch_bounds__(256) bwmu_v_term_kernel(const float* __restric
                                                           const float* __restrict__ Mb, int64_t mstride,
                                                           const int32_t* __restrict__ m_index, int64_t ld, int n, int c,
                                                           double beta, int kind, double* __restrict__ out) {
-  __shared__ double red[256];
   const int tid = threadIdx.x;
   const float* V = Vb + (size_t)blockIdx.x * vstride;
   const float* M = bwmu_weights(Mb, mstride, m_index, blockIdx.x);
-  const double e = (double)kEps;
   double s = 0.0;
   for (int64_t at = tid; at < (int64_t)n * c; at += 256) {
     const size_t off = (size_t)(at / c) * ld + at % c;
     const float m = M[off];
-    if (!(m > 0.f)) continue;
-    const double v = (double)V[off];
-    double t;
-    if (kind == NMFMU_BETA_KL) t = v * log(v + e) - v;
-    else if (kind == NMFMU_BETA_IS) t = -log(v + e) - 1.0;
-    else t = pow(beta < 0.0 ? v + e : v, beta);
-    s += (double)m * t;
+    if (m > 0.f) s += (double)m * bmu_v_term((double)V[off], beta, kind);
   }
-  red[tid] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) red[tid] += red[tid + o];
-    __syncthreads();
-  }
-  if (tid == 0) out[blockIdx.x] = kind == NMFMU_BETA_EUC ? 0.0 : red[0];
+  s = block_sum_256(s);
+  if (tid == 0) out[blockIdx.x] = kind == NMFMU_BETA_EUC ? 0.0 : s;
 }
 
 // One workgroup; one thread per problem (strided over the batch).  nmf.py:402-407 in double on loss = sqrt(2 div) (NaN for
@@ -508,10 +484,8 @@ __global__ void __launch_bounds__(256) bmu_judge_kernel(int batch, const double*
                                                         const double* __restrict__ loss_init, double* __restrict__ previous,
                                                         double tol, int iteration, int32_t* __restrict__ active,
                                                         int64_t* __restrict__ n_iter, int32_t* __restrict__ n_active) {
-  __shared__ int red[256];
-  const int tid = threadIdx.x;
   int alive = 0;
-  for (int b = tid; b < batch; b += 256) {
+  for (int b = threadIdx.x; b < batch; b += 256) {
     if (!active[b]) continue;
     const double d = 2.0 * div[b];
     const double loss = d >= 0.0 ? sqrt(d) : __longlong_as_double(0x7ff8000000000000ll);
@@ -523,13 +497,8 @@ __global__ void __launch_bounds__(256) bmu_judge_kernel(int batch, const double*
       ++alive;
     }
   }
-  red[tid] = alive;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) red[tid] += red[tid + o];
-    __syncthreads();
-  }
-  if (tid == 0) *n_active = red[0];
+  alive = block_sum_256(alive);
+  if (threadIdx.x == 0) *n_active = alive;
 }
 
 }  // namespace nmfmu
@@ -537,24 +506,16 @@ __global__ void __launch_bounds__(256) bmu_judge_kernel(int batch, const double*
 using namespace nmfmu;
 
 namespace {
-constexpr int kFinishBlocks = 4096;      // the finish kernel's workgroups per problem, at most
-
 // NMFMU_OK or the answer the entries give before any device work
 int bmu_check(const void* V, int64_t vstride, int64_t ld, int batch, int n, int c, const void* owner, const void* panel,
               int rank, int r_pad, bool has_r_pad) {
-  if (!V || !owner || !panel || batch <= 0 || n <= 0 || c <= 0 || ld < c || vstride < 0) return NMFMU_ERR_ARG;
-  if (rank <= 0) return NMFMU_ERR_ARG;
-  if (rank > 256) return NMFMU_ERR_UNSUPPORTED;
-  if (has_r_pad && r_pad != nmfmu_pad_rank(rank)) return NMFMU_ERR_ARG;
-  return NMFMU_OK;
+  return wmu_check(batch > 0 && n > 0 && c > 0 && ld >= c && vstride >= 0, V, owner, panel, rank, r_pad, has_r_pad);
 }
 
 // the weights' own arguments: a negative stride, or an index without weights to index
 int bwmu_check(const void* M, int64_t mstride, const void* m_index) {
   return (mstride < 0 || (m_index && !M)) ? NMFMU_ERR_ARG : NMFMU_OK;
 }
-
-int bmu_finish_blocks(int64_t plane) { return (int)std::min<int64_t>((plane + 255) / 256, kFinishBlocks); }
 
 bool bmu_grid_fits(int batch, int64_t blocks_per_problem) { return (int64_t)batch * blocks_per_problem <= INT_MAX; }
 
@@ -566,37 +527,34 @@ int bmu_launch(const float* V, int64_t vstride, const float* M, int64_t mstride,
   const int rows = side ? c : n, contraction = side ? n : c;
   const int parts = wmu_split(rows, contraction, r_pad, nsplit);
   const int part_len = wmu_part_len(contraction, parts);
-  const int64_t plane = (int64_t)rows * r_pad;
-  const int row_tiles = (rows + kWmRows - 1) / kWmRows, fblocks = bmu_finish_blocks(plane);
-  if (!bmu_grid_fits(batch, row_tiles) || !bmu_grid_fits(batch, fblocks)) return NMFMU_ERR_UNSUPPORTED;
-  const bool direct = !step && parts == 1;       // one part of terms: the kernel's planes are the result
-  float* on = direct ? num : ws;
-  float* od = direct ? den : ws + plane;
-  const int64_t pstride = 2 * plane, bstride = direct ? plane : (int64_t)parts * 2 * plane;
-  const dim3 grid((unsigned)(batch * row_tiles), (r_pad + 127) / 128, parts);
+  const WmuSlab sl = wmu_slab(batch, rows, r_pad, parts, step, ws, num, den);
+  if (!bmu_grid_fits(batch, sl.row_tiles) || !bmu_grid_fits(batch, sl.fblocks)) return NMFMU_ERR_UNSUPPORTED;
   for_rp(r_pad, [&](auto rp) {
     for_kind(nmfmu_beta_kind(beta), [&](auto k) {
       constexpr int RP = decltype(rp)::value, KIND = decltype(k)::value;
       if (M && side)
-        hipLaunchKernelGGL((bwmu_kernel<RP, true, KIND>), grid, dim3(256), 0, st, V, vstride, M, mstride, m_index, ld, rows,
-                           contraction, owner, panel, rank, beta, part_len, row_tiles, active, on, od, pstride, bstride);
+        hipLaunchKernelGGL((bwmu_kernel<RP, true, KIND>), sl.grid, dim3(256), 0, st, V, vstride, M, mstride, m_index, ld, rows,
+                           contraction, owner, panel, rank, beta, part_len, sl.row_tiles, active, sl.on, sl.od, sl.pstride,
+                           sl.bstride);
       else if (M)
-        hipLaunchKernelGGL((bwmu_kernel<RP, false, KIND>), grid, dim3(256), 0, st, V, vstride, M, mstride, m_index, ld, rows,
-                           contraction, owner, panel, rank, beta, part_len, row_tiles, active, on, od, pstride, bstride);
+        hipLaunchKernelGGL((bwmu_kernel<RP, false, KIND>), sl.grid, dim3(256), 0, st, V, vstride, M, mstride, m_index, ld, rows,
+                           contraction, owner, panel, rank, beta, part_len, sl.row_tiles, active, sl.on, sl.od, sl.pstride,
+                           sl.bstride);
       else if (side)
-        hipLaunchKernelGGL((bmu_kernel<RP, true, KIND>), grid, dim3(256), 0, st, V, vstride, ld, rows, contraction, owner,
-                           panel, rank, beta, part_len, row_tiles, active, on, od, pstride, bstride);
+        hipLaunchKernelGGL((bmu_kernel<RP, true, KIND>), sl.grid, dim3(256), 0, st, V, vstride, ld, rows, contraction, owner,
+                           panel, rank, beta, part_len, sl.row_tiles, active, sl.on, sl.od, sl.pstride, sl.bstride);
       else
-        hipLaunchKernelGGL((bmu_kernel<RP, false, KIND>), grid, dim3(256), 0, st, V, vstride, ld, rows, contraction, owner,
-                           panel, rank, beta, part_len, row_tiles, active, on, od, pstride, bstride);
+        hipLaunchKernelGGL((bmu_kernel<RP, false, KIND>), sl.grid, dim3(256), 0, st, V, vstride, ld, rows, contraction, owner,
+                           panel, rank, beta, part_len, sl.row_tiles, active, sl.on, sl.od, sl.pstride, sl.bstride);
     });
   });
-  if (!direct && reg)
-    hipLaunchKernelGGL(bmu_finish_reg_kernel, dim3((unsigned)(batch * fblocks)), dim3(256), 0, st, ws, parts, rows, rank, r_pad,
-                       owner, num, den, step, ap, fblocks, active, reg);
-  else if (!direct)
-    hipLaunchKernelGGL(bmu_finish_kernel, dim3((unsigned)(batch * fblocks)), dim3(256), 0, st, ws, parts, rows, rank, r_pad,
-                       owner, num, den, step, ap, fblocks, active);
+  const dim3 fgrid((unsigned)(batch * sl.fblocks));
+  if (!sl.direct && reg)
+    hipLaunchKernelGGL(bmu_finish_reg_kernel, fgrid, dim3(256), 0, st, ws, parts, rows, rank, r_pad, owner, num, den, step, ap,
+                       sl.fblocks, active, reg);
+  else if (!sl.direct)
+    hipLaunchKernelGGL(bmu_finish_kernel, fgrid, dim3(256), 0, st, ws, parts, rows, rank, r_pad, owner, num, den, step, ap,
+                       sl.fblocks, active);
   return (int)hipGetLastError();
 }
 
@@ -667,11 +625,8 @@ int nmfmu_bwmu_loss(const float* V, int64_t v_batch_stride, const float* M, int6
                            beta, part_len, nparts, nblk, active, part);
     });
   });
-  // metrics.py:39 halves the sum of squares; metrics.py:96 divides by beta (beta - 1)
-  double mul = 1.0;
-  if (kind == NMFMU_BETA_EUC) mul = 0.5;
-  if (kind == NMFMU_BETA_GEN) mul = 1.0 / ((double)beta * ((double)beta - 1.0));
-  hipLaunchKernelGGL(bmu_reduce_kernel, dim3(batch), dim3(256), 0, S(stream), part, nblk, v_term, mul, active, out);
+  hipLaunchKernelGGL(bmu_reduce_kernel, dim3(batch), dim3(256), 0, S(stream), part, nblk, v_term,
+                     beta_loss_mul(kind, beta), active, out);
   return (int)hipGetLastError();
 }
 

@@ -318,10 +318,8 @@ NtfMode ntf_mode(int I, int J, int K, int mode) {
 // NMFMU_OK or the answer the entries give before any device work
 int ntf_check(const void* V, int I, int J, int K, int mode, const void* owner, const void* pa, const void* pb, int rank,
               int r_pad, bool has_r_pad, int nsplit = 0) {
-  if (!V || !owner || !pa || !pb || I <= 0 || J <= 0 || K <= 0 || mode < 0 || mode > 2) return NMFMU_ERR_ARG;
-  if (rank <= 0) return NMFMU_ERR_ARG;
-  if (rank > 256) return NMFMU_ERR_UNSUPPORTED;
-  if (has_r_pad && r_pad != nmfmu_pad_rank(rank)) return NMFMU_ERR_ARG;
+  if (const int rc = wmu_check(pb && I > 0 && J > 0 && K > 0 && mode >= 0 && mode <= 2, V, owner, pa, rank, r_pad, has_r_pad))
+    return rc;
   const NtfMode md = ntf_mode(I, J, K, mode);
   if ((int64_t)md.nA * md.nB > kNtfMaxContraction) return NMFMU_ERR_UNSUPPORTED;
   if (has_r_pad && ntf_split(md.rows, md.nA * md.nB, r_pad, nsplit) > kNtfMaxParts) return NMFMU_ERR_UNSUPPORTED;   // a forced split
@@ -335,27 +333,21 @@ int ntf_launch(const float* V, const float* M, int I, int J, int K, int mode, fl
   const int rows = md.rows, contraction = md.nA * md.nB;
   const int parts = ntf_split(rows, contraction, r_pad, nsplit);
   const int part_len = wmu_part_len(contraction, parts);
-  const int64_t plane = (int64_t)rows * r_pad;
-  const bool direct = !step && parts == 1;       // one part of terms: the kernel's planes are the result
-  float* on = direct ? num : ws;
-  float* od = direct ? den : ws + plane;
-  const dim3 grid((rows + kWmRows - 1) / kWmRows, (r_pad + 127) / 128, parts);
+  const WmuSlab sl = wmu_slab(1, rows, r_pad, parts, step, ws, num, den);
   for_rp(r_pad, [&](auto rp) {
     for_kind(nmfmu_beta_kind(beta), [&](auto k) {
       constexpr int RP = decltype(rp)::value, KIND = decltype(k)::value;
       if (md.outer)
-        hipLaunchKernelGGL((ntf_kernel<RP, true, KIND>), grid, dim3(256), 0, st, V, M, md.sO, md.sA, rows, md.nB, contraction,
-                           owner, pa, pb, rank, beta, part_len, on, od, 2 * plane);
+        hipLaunchKernelGGL((ntf_kernel<RP, true, KIND>), sl.grid, dim3(256), 0, st, V, M, md.sO, md.sA, rows, md.nB, contraction,
+                           owner, pa, pb, rank, beta, part_len, sl.on, sl.od, sl.pstride);
       else
-        hipLaunchKernelGGL((ntf_kernel<RP, false, KIND>), grid, dim3(256), 0, st, V, M, md.sO, md.sA, rows, md.nB, contraction,
-                           owner, pa, pb, rank, beta, part_len, on, od, 2 * plane);
+        hipLaunchKernelGGL((ntf_kernel<RP, false, KIND>), sl.grid, dim3(256), 0, st, V, M, md.sO, md.sA, rows, md.nB, contraction,
+                           owner, pa, pb, rank, beta, part_len, sl.on, sl.od, sl.pstride);
     });
   });
-  if (!direct) {
-    const int fgrid = (int)std::min<int64_t>((plane + 255) / 256, 4096);
-    hipLaunchKernelGGL(ntf_finish_kernel, dim3(fgrid), dim3(256), 0, st, ws, parts, rows, rank, r_pad, owner, num, den, step,
-                       ap);
-  }
+  if (!sl.direct)
+    hipLaunchKernelGGL(ntf_finish_kernel, dim3(sl.fblocks), dim3(256), 0, st, ws, parts, rows, rank, r_pad, owner, num, den,
+                       step, ap);
   return (int)hipGetLastError();
 }
 
@@ -411,11 +403,8 @@ int nmfmu_ntf_loss(const float* V, const float* M, int I, int J, int K, const fl
                          (int64_t)JK, (int64_t)K, I, K, JK, A, B, C, rank, beta, part_len, nparts, part);
     });
   });
-  // metrics.py:39 halves the sum of squares; metrics.py:96 divides by beta (beta - 1)
-  double mul = 1.0;
-  if (kind == NMFMU_BETA_EUC) mul = 0.5;
-  if (kind == NMFMU_BETA_GEN) mul = 1.0 / ((double)beta * ((double)beta - 1.0));
-  hipLaunchKernelGGL(sp_reduce_kernel, dim3(1), dim3(256), 0, S(stream), part, nblk, v_term, mul, out);
+  hipLaunchKernelGGL(sp_reduce_kernel, dim3(1), dim3(256), 0, S(stream), part, nblk, v_term, beta_loss_mul(kind, beta),
+                     out);
   return (int)hipGetLastError();
 }
 

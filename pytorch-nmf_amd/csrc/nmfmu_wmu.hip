@@ -183,14 +183,9 @@ __global__ void __launch_bounds__(256) wmu_loss_kernel(const float* __restrict__
 using namespace nmfmu;
 
 namespace {
-// NMFMU_OK or the answer the entries give before any device work
-int wmu_check(const void* V, const void* M, int64_t ld, int n, int c, const void* owner, const void* panel, int rank,
-              int r_pad, bool has_r_pad) {
-  if (!V || !M || !owner || !panel || n <= 0 || c <= 0 || ld < c) return NMFMU_ERR_ARG;
-  if (rank <= 0) return NMFMU_ERR_ARG;
-  if (rank > 256) return NMFMU_ERR_UNSUPPORTED;
-  if (has_r_pad && r_pad != nmfmu_pad_rank(rank)) return NMFMU_ERR_ARG;
-  return NMFMU_OK;
+int wmu_dense_check(const void* V, const void* M, int64_t ld, int n, int c, const void* owner, const void* panel, int rank,
+                    int r_pad, bool has_r_pad) {
+  return wmu_check(M && n > 0 && c > 0 && ld >= c, V, owner, panel, rank, r_pad, has_r_pad);
 }
 
 int wmu_launch(const float* V, const float* M, int64_t ld, int n, int c, int side, float* owner, const float* panel, int rank,
@@ -199,27 +194,21 @@ int wmu_launch(const float* V, const float* M, int64_t ld, int n, int c, int sid
   const int rows = side ? c : n, contraction = side ? n : c;
   const int parts = wmu_split(rows, contraction, r_pad, nsplit);
   const int part_len = wmu_part_len(contraction, parts);
-  const int64_t plane = (int64_t)rows * r_pad;
-  const bool direct = !step && parts == 1;       // one part of terms: the kernel's planes are the result
-  float* on = direct ? num : ws;
-  float* od = direct ? den : ws + plane;
-  const dim3 grid((rows + kWmRows - 1) / kWmRows, (r_pad + 127) / 128, parts);
+  const WmuSlab sl = wmu_slab(1, rows, r_pad, parts, step, ws, num, den);
   for_rp(r_pad, [&](auto rp) {
     for_kind(nmfmu_beta_kind(beta), [&](auto k) {
       constexpr int RP = decltype(rp)::value, KIND = decltype(k)::value;
       if (side)
-        hipLaunchKernelGGL((wmu_kernel<RP, true, KIND>), grid, dim3(256), 0, st, V, M, ld, rows, contraction, owner, panel,
-                           rank, beta, part_len, on, od, 2 * plane);
+        hipLaunchKernelGGL((wmu_kernel<RP, true, KIND>), sl.grid, dim3(256), 0, st, V, M, ld, rows, contraction, owner, panel,
+                           rank, beta, part_len, sl.on, sl.od, sl.pstride);
       else
-        hipLaunchKernelGGL((wmu_kernel<RP, false, KIND>), grid, dim3(256), 0, st, V, M, ld, rows, contraction, owner, panel,
-                           rank, beta, part_len, on, od, 2 * plane);
+        hipLaunchKernelGGL((wmu_kernel<RP, false, KIND>), sl.grid, dim3(256), 0, st, V, M, ld, rows, contraction, owner, panel,
+                           rank, beta, part_len, sl.on, sl.od, sl.pstride);
     });
   });
-  if (!direct) {
-    const int fgrid = (int)std::min<int64_t>((plane + 255) / 256, 4096);
-    hipLaunchKernelGGL(wmu_finish_kernel, dim3(fgrid), dim3(256), 0, st, ws, parts, rows, rank, r_pad, owner, num, den, step,
-                       ap);
-  }
+  if (!sl.direct)
+    hipLaunchKernelGGL(wmu_finish_kernel, dim3(sl.fblocks), dim3(256), 0, st, ws, parts, rows, rank, r_pad, owner, num, den,
+                       step, ap);
   return (int)hipGetLastError();
 }
 
@@ -242,7 +231,7 @@ int nmfmu_wmu_terms(const float* V, const float* M, int64_t ld, int n, int c, in
                     const float* panel, int rank, int r_pad, float beta, int nsplit, float* ws, float* num, float* den,
                     void* stream) {
   if (!ws || !num || !den || nsplit < 0 || (side != 0 && side != 1)) return NMFMU_ERR_ARG;
-  if (const int rc = wmu_check(V, M, ld, n, c, owner, panel, rank, r_pad, true)) return rc;
+  if (const int rc = wmu_dense_check(V, M, ld, n, c, owner, panel, rank, r_pad, true)) return rc;
   return wmu_launch(V, M, ld, n, c, side, const_cast<float*>(owner), panel, rank, r_pad, beta, nsplit, ws, num, den, 0,
                     MaskedApply{0.f, 0.f, 1.f}, S(stream));
 }
@@ -250,7 +239,7 @@ int nmfmu_wmu_terms(const float* V, const float* M, int64_t ld, int n, int c, in
 int nmfmu_wmu_step(const float* V, const float* M, int64_t ld, int n, int c, int side, float* owner, const float* panel,
                    int rank, int r_pad, float beta, float l1, float l2, float gamma, int nsplit, float* ws, void* stream) {
   if (!ws || owner == panel || nsplit < 0 || (side != 0 && side != 1)) return NMFMU_ERR_ARG;
-  if (const int rc = wmu_check(V, M, ld, n, c, owner, panel, rank, r_pad, true)) return rc;
+  if (const int rc = wmu_dense_check(V, M, ld, n, c, owner, panel, rank, r_pad, true)) return rc;
   return wmu_launch(V, M, ld, n, c, side, owner, panel, rank, r_pad, beta, nsplit, ws, nullptr, nullptr, 1,
                     MaskedApply{l1, l2, gamma}, S(stream));
 }
@@ -263,7 +252,7 @@ int nmfmu_wmu_loss_parts(int n, int c) {
 int nmfmu_wmu_loss(const float* V, const float* M, int64_t ld, int n, int c, const float* H, const float* W, int rank,
                    float beta, double v_term, double* part, double* out, void* stream) {
   if (!part || !out) return NMFMU_ERR_ARG;
-  if (const int rc = wmu_check(V, M, ld, n, c, H, W, rank, 0, false)) return rc;
+  if (const int rc = wmu_dense_check(V, M, ld, n, c, H, W, rank, 0, false)) return rc;
   const int nparts = wmu_loss_split(n, c), part_len = wmu_part_len(c, nparts);
   const int nblk = (n + kWmRows - 1) / kWmRows * nparts;
   const int kind = nmfmu_beta_kind(beta);
@@ -273,11 +262,8 @@ int nmfmu_wmu_loss(const float* V, const float* M, int64_t ld, int n, int c, con
                          M, ld, n, c, H, W, rank, beta, part_len, nparts, part);
     });
   });
-  // metrics.py:39 halves the sum of squares; metrics.py:96 divides by beta (beta - 1)
-  double mul = 1.0;
-  if (kind == NMFMU_BETA_EUC) mul = 0.5;
-  if (kind == NMFMU_BETA_GEN) mul = 1.0 / ((double)beta * ((double)beta - 1.0));
-  hipLaunchKernelGGL(sp_reduce_kernel, dim3(1), dim3(256), 0, S(stream), part, nblk, v_term, mul, out);
+  hipLaunchKernelGGL(sp_reduce_kernel, dim3(1), dim3(256), 0, S(stream), part, nblk, v_term, beta_loss_mul(kind, beta),
+                     out);
   return (int)hipGetLastError();
 }
 

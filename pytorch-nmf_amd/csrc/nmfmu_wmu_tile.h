@@ -1,9 +1,12 @@
-// The tile pieces the exact-fp32 MFMA kernels on the fp32 masters share: the weighted dense kernels (nmfmu_wmu.hip) and their
-// batched siblings, unweighted and weighted (nmfmu_bmu.hip).  A workgroup (4 waves) owns 128 owner rows x a rank tile of
-// <= 128 x one part of the contraction axis; a stage is 32 contraction steps.  Here: the tile plan (WmuCfg), the split rule of
-// the contraction, the owner rows in registers, the panel rows on their way to LDS, Y = owner x panel over the full padded
-// rank, the weighted stage (V and M on their way to LDS) and the dispatch over the padded rank.  A kernel's seeds and its
-// epilogue stay in its own file.
+// The tile pieces the exact-fp32 MFMA kernels on the fp32 masters share: the weighted dense kernels (nmfmu_wmu.hip), their
+// batched siblings, unweighted and weighted (nmfmu_bmu.hip), and the 3-way tensor kernels (nmfmu_ntf.hip).  A workgroup
+// (4 waves) owns 128 owner rows x a rank tile of <= 128 x one part of the contraction axis; a stage is 32 contraction steps.
+// Here: the tile plan (WmuCfg), the split rule of the contraction, the owner rows in registers, the panel rows on their way to
+// LDS, Y = owner x panel over the full padded rank, the weighted stage (V and M on their way to LDS), the workgroup sum of the
+// small reduction kernels and, on the host, the slab plan of a launch, the divergence scale, the common argument checks and
+// the dispatch over the padded rank.  A kernel's stage loop, its seeds and its epilogue stay in its own file: a stage loop
+// shared as one inlined body compiled to other register allocations and MFMA-loop schedules and measured slower on the batched
+// fit (profiles/tile_refactor_ab.md).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -11,6 +14,7 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "../../include/nmfmu.h"
 #include "nmfmu_fused.h"
 
 namespace nmfmu {
@@ -21,6 +25,7 @@ constexpr int kWmLDA = kWmBK + 1;    // sv / sm [i][c]: lanes read a column (sec
 constexpr int kWmTargetWgs = 512;    // two workgroups on each of the 256 CUs
 constexpr int kWmMinStages = 4;      // the library's own parts are at least 128 contraction steps long ...
 constexpr int kWmMaxSplit = 64;      // ... and there are at most 64 of them
+constexpr int kWmFinishBlocks = 4096; // the finish kernel's workgroups per problem, at most
 
 template <int RP>
 struct WmuCfg {
@@ -147,6 +152,63 @@ __device__ __forceinline__ void wmu_store_vm(float* sv, float* sm, const WmuStag
       sv[at] = st.av[p][q], sm[at] = st.mv[p][q];
     }
   }
+}
+
+// the sum of every thread's s over a workgroup of 256, by a halving tree: a pure function of the 256 values.  Once per
+// kernel: red[0] is read behind the last barrier with none after it, so a second call could overwrite it under a slow reader.
+template <class T>
+__device__ __forceinline__ T block_sum_256(T s) {
+  __shared__ T red[256];
+  const int tid = threadIdx.x;
+  red[tid] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) red[tid] += red[tid + o];
+    __syncthreads();
+  }
+  return red[0];
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------------------
+// Where a launch of `parts` parts over `batch` problems puts its planes: every part to the slab ws [problem][part][num | den]
+// [rows][r_pad] and a finish launch of fblocks workgroups per problem behind it, or -- one part of terms -- the kernel's
+// planes are the result (direct: no finish).  on / od + problem * bstride + part * pstride are the part's planes.
+struct WmuSlab {
+  int row_tiles, fblocks;
+  dim3 grid;      // (problems x row tiles, rank tiles, parts)
+  bool direct;
+  float *on, *od;
+  int64_t pstride, bstride;
+};
+
+inline WmuSlab wmu_slab(int batch, int rows, int r_pad, int parts, int step, float* ws, float* num, float* den) {
+  const int64_t plane = (int64_t)rows * r_pad;
+  WmuSlab s;
+  s.row_tiles = (rows + kWmRows - 1) / kWmRows;
+  s.fblocks = (int)std::min<int64_t>((plane + 255) / 256, kWmFinishBlocks);
+  s.grid = dim3((unsigned)((int64_t)batch * s.row_tiles), (r_pad + 127) / 128, parts);
+  s.direct = !step && parts == 1;
+  s.on = s.direct ? num : ws;
+  s.od = s.direct ? den : ws + plane;
+  s.pstride = 2 * plane;
+  s.bstride = s.direct ? plane : (int64_t)parts * 2 * plane;
+  return s;
+}
+
+// what the divergence's sum is multiplied by: metrics.py:39 halves the sum of squares; metrics.py:96 divides by beta (beta - 1)
+inline double beta_loss_mul(int kind, float beta) {
+  if (kind == NMFMU_BETA_EUC) return 0.5;
+  if (kind == NMFMU_BETA_GEN) return 1.0 / ((double)beta * ((double)beta - 1.0));
+  return 1.0;
+}
+
+// NMFMU_OK or the answer the entries give before any device work.  args_ok: the entry's own sizes and pointers.
+inline int wmu_check(bool args_ok, const void* V, const void* owner, const void* panel, int rank, int r_pad, bool has_r_pad) {
+  if (!args_ok || !V || !owner || !panel) return NMFMU_ERR_ARG;
+  if (rank <= 0) return NMFMU_ERR_ARG;
+  if (rank > 256) return NMFMU_ERR_UNSUPPORTED;
+  if (has_r_pad && r_pad != nmfmu_pad_rank(rank)) return NMFMU_ERR_ARG;
+  return NMFMU_OK;
 }
 
 // f(std::integral_constant<int, r_pad>)
