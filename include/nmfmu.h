@@ -96,6 +96,9 @@ extern "C" {
                                   nmfmu_ntf_terms / nmfmu_ntf_step / nmfmu_ntf_loss / nmfmu_ntf_ws / nmfmu_ntf_nsplit /
                                   nmfmu_ntf_loss_parts (ntf.NTF: non-negative CP factorisation of a 3-way tensor walked in
                                   place, Khatri-Rao rows formed in LDS; added at ABI 10, additive);
+                                  nmfmu_sp_ntf_terms / nmfmu_sp_ntf_step / nmfmu_sp_ntf_loss / nmfmu_sp_ntf_ws /
+                                  nmfmu_sp_ntf_lds_rows (ntf.NTF on sparse-COO tensors: the fit over the stored entries,
+                                  unstored = 'missing' | 'zero'; added at ABI 10, additive);
                                10: nmfmu_plca_normalize / nmfmu_plca_z / nmfmu_plca3 take alpha as double (an argument changed its
                                   type: not additive).  The Dirichlet prior adds fp32(alpha - 1) with the subtraction in double,
                                   as the reference's in-place add does; fp32(alpha) - 1.f was off by 4.7e-5 relative at
@@ -995,6 +998,47 @@ int nmfmu_ntf_step(const float* V, const float* M, int I, int J, int K, int mode
 int nmfmu_ntf_loss_parts(int I, int J, int K);
 int nmfmu_ntf_loss(const float* V, const float* M, int I, int J, int K, const float* A, const float* B, const float* C, int rank,
                    float beta, double v_term, double* part, double* out, void* stream);
+
+/* ---- NTF on a sparse 3-way target: the fit over the STORED entries (additive entries) -----------------------------------------
+ * Per mode the target is held sorted by (owner index, a, b), a < b the other two modes: seg / multi are the segment lists of
+ * nmfmu_sp_div_backward over the owner's rowptr, idx_a / idx_b [nnz] the int32 rows of the panel factors pa [rows_a][rank] and
+ * pb [rows_b][rank], vals [nnz] the values in that order.  For a stored entry p of owner row i
+ *   kr_p = fl32(pa[idx_a[p]] o pb[idx_b[p]]) (registers only),  s_p = <owner[i], kr_p>,  num[i] = sum_p g_neg(v_p, s_p) kr_p
+ * zero == 0 (unstored = 'missing', every beta): den[i] = sum_p g_pos(s_p) kr_p, g_neg / g_pos as for nmfmu_sp_masked_*.
+ * zero == 1 (unstored = 'zero', beta in {1, 2}; another beta: NMFMU_ERR_UNSUPPORTED): every unstored entry is an observed
+ * zero, the denominator factorises and is an INPUT in the pos / pos_plane convention of nmfmu_sp_div_backward -- beta 1:
+ * pos_plane 0, pos = the [r_pad] vector colsum(pa) o colsum(pb); beta 2: pos_plane 1, pos = [owner rows][r_pad] =
+ * owner @ (gram(pa) o gram(pb)), and g_neg = v so that no dot product is formed.  pos is ignored when zero == 0.
+ * Entries accumulate in storage order, a split row's partial rows (ws slots) in segment order: plain stores only, no atomics
+ * -- a repeated call is bitwise identical.
+ *   nmfmu_sp_ntf_lds_rows : a panel factor of at most this many rows can be copied into LDS once per workgroup, its gather
+ *                           then reads LDS (7936 / rank; 0 outside rank 1 .. 256).  Workgroups on that route are persistent.
+ *                           stage: 0 -- the library's rule, a pure function of the counts (as measured so far: stage nothing);
+ *                           1 -- never; 2 -- every panel that fits.  The results do not depend on it.
+ *   nmfmu_sp_ntf_ws       : floats of `ws` = (sum of `segments` over multi) * 2 * r_pad ('zero' uses the first half)
+ *   nmfmu_sp_ntf_terms    : num, den [owner rows][r_pad], zeros in the padded columns; under 'zero' den = pos, broadcast
+ *   nmfmu_sp_ntf_step     : the same terms, then nmf.py:78-92 in place on the owner's fp32 master; owner != pa, pb
+ *   nmfmu_sp_ntf_loss     : from mode 0's list (owner = A, pa = B, pb = C), summed in double per lane, wave, segment quad,
+ *                           then in quad order; part: (n_seg + 3) / 4 doubles.  zero == 0: *out = metrics.beta_div(s, v, beta)
+ *                           over the stored entries, v_term as for nmfmu_sp_masked_loss.  zero == 1: *out = v_term - neg,
+ *                           neg = sum_p v_p log(s_p + eps) (beta 1) | sum_p v_p s_p (beta 2); the caller adds the positive
+ *                           part, sum_r csA csB csC | 1/2 sum (gram A o gram B o gram C).
+ * Null pointers, n_seg <= 0, n_multi < 0, nnz < 0, rows_a / rows_b <= 0, rank <= 0, zero not 0 / 1, stage not 0 .. 2,
+ * r_pad != nmfmu_pad_rank(rank), pos NULL with zero == 1: NMFMU_ERR_ARG; rank > 256: NMFMU_ERR_UNSUPPORTED -- both before any
+ * device work. */
+int nmfmu_sp_ntf_lds_rows(int rank);
+int64_t nmfmu_sp_ntf_ws(int n_multi_segments, int r_pad);
+int nmfmu_sp_ntf_terms(const int32_t* seg, int n_seg, const int32_t* multi, int n_multi, const int32_t* idx_a,
+                       const int32_t* idx_b, const float* vals, int nnz, const float* owner, const float* pa, int rows_a,
+                       const float* pb, int rows_b, int rank, float beta, int zero, const float* pos, int pos_plane,
+                       float* ws, float* num, float* den, int r_pad, int stage, void* stream);
+int nmfmu_sp_ntf_step(const int32_t* seg, int n_seg, const int32_t* multi, int n_multi, const int32_t* idx_a,
+                      const int32_t* idx_b, const float* vals, int nnz, float* owner, const float* pa, int rows_a,
+                      const float* pb, int rows_b, int rank, float beta, int zero, const float* pos, int pos_plane, float l1,
+                      float l2, float gamma, float* ws, int r_pad, int stage, void* stream);
+int nmfmu_sp_ntf_loss(const int32_t* seg, int n_seg, const int32_t* idx_a, const int32_t* idx_b, const float* vals, int nnz,
+                      const float* owner, const float* pa, int rows_a, const float* pb, int rows_b, int rank, float beta,
+                      int zero, double v_term, double* part, double* out, int stage, void* stream);
 
 /* ---- PLCA's EM update (plca.py:248-290) -----------------------------------------------------------------------------
  * With G = Vn / (H diag(Z) W^T + eps) the factor "gradients" are (G^T H) * Z, (G W) * Z and Z.grad[r] = sum W * (G^T H);

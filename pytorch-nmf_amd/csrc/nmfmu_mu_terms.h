@@ -42,6 +42,19 @@ __device__ __forceinline__ float masked_apply(float f, float num, float den, con
   return f * mult;
 }
 
+// the epilogue of a finished owner row of the stored-entry kernels (nmfmu_sparse_masked.hip, nmfmu_sparse_ntf.hip): r < r_pad,
+// f = owner[row][r] (step only).  step: the update in place; otherwise the two planes, zeros in the padded rank columns
+__device__ __forceinline__ void masked_finish(int step, float* owner, float* __restrict__ num, float* __restrict__ den,
+                                              int row, int r, int rank, int r_pad, float f, float n, float d,
+                                              const MaskedApply& ap) {
+  if (step) {
+    if (r < rank) owner[(size_t)row * rank + r] = masked_apply(f, n, d, ap);
+  } else {
+    num[(size_t)row * r_pad + r] = r < rank ? n : 0.f;
+    den[(size_t)row * r_pad + r] = r < rank ? d : 0.f;
+  }
+}
+
 // the s-dependent term of metrics.beta_div at one entry, in double (see nmfmu_sp_masked_loss in include/nmfmu.h)
 template <int KIND>
 __device__ __forceinline__ double masked_loss_term(float v, float s, float beta) {

@@ -27,18 +27,6 @@
 
 namespace nmfmu {
 
-// the shared epilogue of a finished row: r < r_pad, f = owner[row][r] (step only)
-__device__ __forceinline__ void masked_finish(int step, float* owner, float* __restrict__ num, float* __restrict__ den,
-                                              int row, int r, int rank, int r_pad, float f, float n, float d,
-                                              const MaskedApply& ap) {
-  if (step) {
-    if (r < rank) owner[(size_t)row * rank + r] = masked_apply(f, n, d, ap);
-  } else {
-    num[(size_t)row * r_pad + r] = r < rank ? n : 0.f;
-    den[(size_t)row * r_pad + r] = r < rank ? d : 0.f;
-  }
-}
-
 template <int RL, int KIND>
 __global__ void __launch_bounds__(256) sp_masked_kernel(const int32_t* __restrict__ seg, int n_seg,
                                                         const int32_t* __restrict__ idx, const float* __restrict__ vals,

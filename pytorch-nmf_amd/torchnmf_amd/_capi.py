@@ -196,6 +196,18 @@ SIGNATURES = {
     'nmfmu_ntf_loss_parts': (C.c_int, [C.c_int, C.c_int, C.c_int]),
     'nmfmu_ntf_loss': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                  C.c_float, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'nmfmu_sp_ntf_lds_rows': (C.c_int, [C.c_int]),
+    'nmfmu_sp_ntf_ws': (C.c_int64, [C.c_int, C.c_int]),
+    'nmfmu_sp_ntf_terms': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                     C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int,
+                                     C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    'nmfmu_sp_ntf_step': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                    C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int,
+                                    C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_int,
+                                    C.c_void_p]),
+    'nmfmu_sp_ntf_loss': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                    C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_double, C.c_void_p,
+                                    C.c_void_p, C.c_int, C.c_void_p]),
     'nmfmu_bmu_nsplit': (C.c_int, [C.c_int, C.c_int, C.c_int]),
     'nmfmu_bmu_ws': (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     'nmfmu_bmu_terms': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,

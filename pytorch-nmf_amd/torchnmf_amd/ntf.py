@@ -5,6 +5,11 @@
 anything there).  One half-step is one ``nmfmu_ntf_step`` call on the fp32 masters: the fused exact-fp32 MFMA kernel of
 csrc/nmfmu_ntf.hip walks the three unfoldings of the row-major tensor in place and forms the Khatri-Rao rows 32 at a time in
 LDS -- nothing of ``V``'s size and no Khatri-Rao matrix is allocated beyond ``V`` and ``M`` themselves.
+
+A 3-D sparse COO tensor is fitted over its STORED entries, ``fit(V_sparse, unstored='missing' | 'zero')``: ``SparseNtfTarget``
+holds one sorted copy per mode, one half-step is one ``nmfmu_sp_ntf_step`` call (csrc/nmfmu_sparse_ntf.hip: two panel rows
+gathered per stored entry and multiplied in registers; under 'zero' the denominator comes from column sums or Gram matrices
+of the factors).  ``sparse_ntf_terms`` / ``sparse_ntf_loss`` are the functional forms.
 """
 from __future__ import annotations
 
@@ -14,12 +19,13 @@ import torch
 from torch import Tensor, nn
 
 from . import _capi
+from . import sparse_autograd as SA
 from .constants import eps
 from .engine import mu_gamma
 from .nmf import _require_device, _sqrt2
 from .wmu import check_weights
 
-__all__ = ['NTF', 'NtfTarget', 'ntf_terms', 'ntf_loss']
+__all__ = ['NTF', 'NtfTarget', 'ntf_terms', 'ntf_loss', 'SparseNtfTarget', 'sparse_ntf_terms', 'sparse_ntf_loss']
 
 MAX_RANK = 256
 MAX_CONTRACTION = 1 << 30      # csrc/nmfmu_ntf.hip: the flat contraction steps of a mode are ints
@@ -157,6 +163,206 @@ def ntf_loss(V, weights, factors: Sequence[Tensor], beta: float) -> Tensor:
     return _ntf_loss(T, fs, float(beta))[0]
 
 
+# ---- sparse targets: the stored entries only ------------------------------------------------------------------------------------
+def plan_sparse_ntf(indices: Tensor, vals: Tensor, shape, chunk: int):
+    """The three sorted copies of a coalesced 3-D COO tensor and their work lists (pure torch, any device).  ``indices``:
+    int64 ``[3, nnz]`` in lexicographic order, as ``coalesce`` leaves them.  Per mode ``n`` a dict with ``rowptr``
+    ``[dim_n + 1]``, ``idx_a`` / ``idx_b`` (int32 rows of the other two factors, ascending mode number), ``vals`` -- all sorted
+    by (owner index, a, b): a stable sort by the owner index of the lexicographic order -- and ``seg`` / ``multi`` / ``n_ws``
+    of ``sparse_autograd.plan_worklist``."""
+    modes = []
+    for n, dim in enumerate(shape):
+        order = None if n == 0 else torch.sort(indices[n], stable=True)[1]
+        own, (ia, ib) = indices[n], (indices[m] for m in range(3) if m != n)
+        if order is not None:
+            own, ia, ib = own[order], ia[order], ib[order]
+        rowptr = torch.zeros(dim + 1, dtype=torch.int64, device=indices.device)
+        rowptr[1:] = torch.cumsum(torch.bincount(own, minlength=dim), 0)
+        rowptr = rowptr.to(torch.int32)
+        seg, multi, n_ws = SA.plan_worklist(rowptr, chunk)
+        modes.append(dict(rowptr=rowptr, idx_a=ia.to(torch.int32).contiguous(), idx_b=ib.to(torch.int32).contiguous(),
+                          vals=(vals if order is None else vals[order]).contiguous(), seg=seg, multi=multi, n_ws=n_ws))
+    return modes
+
+
+class SparseNtfTarget:
+    """A 3-D sparse-COO target prepared once on the device: coalesced, one copy per mode sorted by (owner index, a, b) with
+    its segment work lists (``plan_sparse_ntf``), the two flags of nmf.py:329-336 over the STORED values and the float64
+    terms of the loss that hold ``v`` alone per (beta, unstored).  ``chunk``: stored entries per segment (``None``: no row is
+    split).  ``nnz`` and every dimension stay below 2^31; the 2^30 contraction limit of the dense kernels does not apply."""
+
+    def __init__(self, V: Tensor, chunk=SA.DEFAULT_CHUNK):
+        if not isinstance(V, Tensor) or not V.is_sparse or V.dim() != 3:
+            raise ValueError('a sparse NTF target is a 3-D sparse COO tensor')
+        if V.device.type != 'cuda':
+            raise _capi.NmfmuError('SparseNtfTarget: the target must live on the ROCm device (no CPU fallback)')
+        V = V.detach().coalesce()
+        if not (V._nnz() < 2 ** 31 and max(V.shape) < 2 ** 31 and min(V.shape) > 0):
+            raise ValueError(f'SparseNtfTarget: nnz ({V._nnz()}) and every dimension of {tuple(V.shape)} must be below 2^31, '
+                             f'and no dimension empty')
+        self.shape, self.device, self.nnz = tuple(V.shape), V.device, int(V._nnz())
+        self.vals = V.values().float()
+        if chunk is None:
+            chunk = max(int(torch.bincount(V.indices()[n], minlength=1).max()) for n in range(3)) if self.nnz else 1
+        self.chunk = int(chunk)
+        self.modes = plan_sparse_ntf(V.indices(), self.vals, self.shape, self.chunk)
+        self.spare = torch.zeros(4, dtype=torch.float32, device=V.device)      # sparse_autograd.entries
+        self.bad = bool((~(self.vals >= 0)).any().item()) if self.nnz else False
+        self.has_zero = bool((self.vals == 0).any().item()) if self.nnz else False
+        self._v_term = {}
+
+    def v_term(self, beta: float, unstored: str) -> float:
+        """What ``nmfmu_sp_ntf_loss`` takes as ``v_term``, in float64.  'missing': the terms of ``metrics.beta_div`` that hold
+        v alone.  'zero': the same at beta 1 (an unstored zero adds nothing), 1/2 sum v^2 at beta 2, where the kernel sums
+        -v s and the positive part carries 1/2 s^2.  Once per (target, beta, unstored); a Python float."""
+        key = (beta, unstored)
+        if key not in self._v_term:
+            if unstored == 'zero' and beta == 2.0:
+                vd = self.vals.double()
+                self._v_term[key] = float((vd @ vd).item() * 0.5)
+            else:
+                self._v_term[key] = SA.masked_v_term(self.vals, beta)
+        return self._v_term[key]
+
+
+def _check_sparse(shape, factors, beta: float, unstored, weights=None) -> None:
+    """The refusals of the sparse path in their documented order, all before the device is asked."""
+    if unstored not in ('zero', 'missing'):
+        raise ValueError(f"unstored must be 'zero' or 'missing', got {unstored!r}")
+    if len(shape) != 3:
+        raise NotImplementedError(f'NTF factorises tensors of order 3, got order {len(shape)}')
+    if tuple(shape) != tuple(f.shape[0] for f in factors):
+        raise ValueError(f'target {tuple(shape)} does not match the factors {tuple(f.shape[0] for f in factors)}')
+    if weights is not None:
+        raise NotImplementedError('NTF.fit on a sparse target takes no weights: the stored set is the mask')
+    if unstored == 'zero' and float(beta) not in (1.0, 2.0):
+        raise NotImplementedError(f"unstored='zero' supports beta in {{1, 2}}, got {float(beta):g}: for any other beta the "
+                                  f"positive term runs over every entry of the tensor; use unstored='missing'")
+    rank = factors[0].shape[1]
+    if rank > MAX_RANK:
+        raise NotImplementedError(f'NTF: rank {rank} > {MAX_RANK}, the limit of the sparse kernels')
+
+
+def _colsum(lib, f: Tensor) -> Tensor:
+    R = f.shape[1]
+    part = torch.empty(R * 128, dtype=torch.float32, device=f.device)
+    cs = torch.empty(R, dtype=torch.float32, device=f.device)
+    _capi.check(lib.nmfmu_rank_sums(f.data_ptr(), f.shape[0], R, 1, part.data_ptr(), cs.data_ptr(), _stream()), 'nmfmu_rank_sums')
+    return cs
+
+
+def _gram(lib, f: Tensor) -> Tensor:
+    R = f.shape[1]
+    part = torch.empty(lib.nmfmu_gram_part_bytes(R) // 4, dtype=torch.float32, device=f.device)
+    g = torch.empty(R * R, dtype=torch.float32, device=f.device)
+    _capi.check(lib.nmfmu_gram(f.data_ptr(), f.shape[0], R, part.data_ptr(), g.data_ptr(), _stream()), 'nmfmu_gram')
+    return g
+
+
+def _zero_pos(lib, owner: Tensor, pa: Tensor, pb: Tensor, beta: float, r_pad: int):
+    """(pos, pos_plane) of ``nmfmu_sp_ntf_*`` under unstored = 'zero': the denominator over EVERY entry of the tensor from
+    the small per-factor terms -- colsum(Pa) o colsum(Pb) (beta 1) or owner @ (Gram(Pa) o Gram(Pb)) (beta 2)."""
+    rows, R = owner.shape
+    if beta == 1.0:
+        pos = torch.zeros(r_pad, dtype=torch.float32, device=owner.device)
+        pos[:R] = _colsum(lib, pa) * _colsum(lib, pb)
+        return pos, 0
+    g = _gram(lib, pa) * _gram(lib, pb)
+    pos = torch.empty(rows * r_pad, dtype=torch.float32, device=owner.device)
+    _capi.check(lib.nmfmu_rowmat(owner.data_ptr(), rows, R, g.data_ptr(), pos.data_ptr(), r_pad, _stream()), 'nmfmu_rowmat')
+    return pos, 1
+
+
+def _sparse_call(T: SparseNtfTarget, factors: Sequence[Tensor], mode: int, beta: float, unstored: str, step=None,
+                 stage: int = 0, _fill=None, _ws=None):
+    """``nmfmu_sp_ntf_terms`` (``step`` None: returns (num, den), fp32 ``[dim_mode, r_pad]``) or ``nmfmu_sp_ntf_step``
+    (``step`` = (l1, l2, gamma): ``factors[mode]`` updated in place).  ``factors``: three contiguous fp32 ``[dim_n, R]``.
+    Enqueued only.  ``stage``: 0 the library's rule, 1 no panel in LDS, 2 every panel that fits.  ``_fill``: tests pre-fill
+    the outputs and the workspace with it."""
+    lib = _capi.load()
+    owner = factors[mode]
+    pa, pb = (f for n, f in enumerate(factors) if n != mode)
+    rows, R = owner.shape
+    assert tuple(f.shape for f in factors) == tuple((d, R) for d in T.shape)
+    r_pad = lib.nmfmu_pad_rank(R)
+    m = T.modes[mode]
+    n_float = lib.nmfmu_sp_ntf_ws(m['n_ws'], r_pad)
+    ws = _ws if _ws is not None else torch.empty(max(n_float, 1), dtype=torch.float32, device=T.device)
+    assert ws.numel() >= n_float
+    if _fill is not None:
+        ws.fill_(_fill)
+    zero = unstored == 'zero'
+    pos, plane = _zero_pos(lib, owner, pa, pb, beta, r_pad) if zero else (None, 0)
+    head = (m['seg'].data_ptr(), m['seg'].shape[0], m['multi'].data_ptr() if m['multi'].shape[0] else None, m['multi'].shape[0],
+            SA.entries(m['idx_a'], T.spare), SA.entries(m['idx_b'], T.spare), SA.entries(m['vals'], T.spare), T.nnz,
+            owner.data_ptr(), pa.data_ptr(), pa.shape[0], pb.data_ptr(), pb.shape[0], R, beta, int(zero),
+            pos.data_ptr() if zero else None, plane)
+    if step is not None:
+        l1, l2, gamma = step
+        _capi.check(lib.nmfmu_sp_ntf_step(*head, l1, l2, gamma, ws.data_ptr(), r_pad, stage, _stream()), 'nmfmu_sp_ntf_step')
+        return None
+    num = torch.empty(rows, r_pad, dtype=torch.float32, device=T.device)
+    den = torch.empty(rows, r_pad, dtype=torch.float32, device=T.device)
+    if _fill is not None:
+        num.fill_(_fill)
+        den.fill_(_fill)
+    _capi.check(lib.nmfmu_sp_ntf_terms(*head, ws.data_ptr(), num.data_ptr(), den.data_ptr(), r_pad, stage, _stream()),
+                'nmfmu_sp_ntf_terms')
+    return num, den
+
+
+def _sparse_loss(T: SparseNtfTarget, factors: Sequence[Tensor], beta: float, unstored: str, stage: int = 0, part=None,
+                 out=None) -> Tensor:
+    """The loss as a 1-element float64 device tensor.  Enqueued only.  Under 'zero' the positive part over every entry of
+    the tensor is added here: ``sum_r csA csB csC`` (beta 1) or ``1/2 sum G_A o G_B o G_C`` (beta 2), float64 on the device."""
+    lib = _capi.load()
+    A, B, Cf = factors
+    m = T.modes[0]
+    n_seg = m['seg'].shape[0]
+    if part is None:
+        part = torch.empty((n_seg + 3) // 4, dtype=torch.float64, device=T.device)
+    if out is None:
+        out = torch.empty(1, dtype=torch.float64, device=T.device)
+    zero = unstored == 'zero'
+    _capi.check(lib.nmfmu_sp_ntf_loss(m['seg'].data_ptr(), n_seg, SA.entries(m['idx_a'], T.spare), SA.entries(m['idx_b'], T.spare),
+                                      SA.entries(m['vals'], T.spare), T.nnz, A.data_ptr(), B.data_ptr(), B.shape[0], Cf.data_ptr(),
+                                      Cf.shape[0], A.shape[1], beta, int(zero), T.v_term(beta, unstored), part.data_ptr(),
+                                      out.data_ptr(), stage, _stream()), 'nmfmu_sp_ntf_loss')
+    if not zero:
+        return out
+    small = [(_colsum if beta == 1.0 else _gram)(lib, f).double() for f in factors]
+    pos = (small[0] * small[1] * small[2]).sum()
+    return out + (pos if beta == 1.0 else 0.5 * pos)
+
+
+def _prepare_sparse(T, factors, beta, unstored):
+    shape = tuple(T.shape)
+    _check_sparse(shape, factors, beta, unstored)
+    for f in factors:
+        _require_device(f, 'NTF')
+    if not isinstance(T, SparseNtfTarget):
+        if not (isinstance(T, Tensor) and T.is_sparse):
+            raise ValueError('the target must be a 3-D sparse COO tensor or a SparseNtfTarget')
+        T = SparseNtfTarget(T)
+    return T, [f.detach().float().contiguous() for f in factors]
+
+
+def sparse_ntf_terms(T, factors: Sequence[Tensor], mode: int, beta: float, unstored: str, stage: int = 0):
+    """``(num, den)`` of the half-step of ``mode`` over the stored entries of ``T`` (a 3-D sparse COO device tensor or a
+    ``SparseNtfTarget`` prepared once), fp32 ``[dim_mode, r_pad]`` with zeros in the padded rank columns; ``den - num`` is
+    the gradient of the loss with respect to ``factors[mode]``.  ``unstored``: 'missing' -- the unstored entries are unknown,
+    every beta; 'zero' -- they are observed zeros, beta in {1, 2}, and ``den`` is the factorised denominator."""
+    T, fs = _prepare_sparse(T, factors, beta, unstored)
+    return _sparse_call(T, fs, int(mode), float(beta), unstored, stage=stage)
+
+
+def sparse_ntf_loss(T, factors: Sequence[Tensor], beta: float, unstored: str, stage: int = 0) -> Tensor:
+    """The beta-divergence between ``T`` and the reconstruction, over the stored entries ('missing') or with every unstored
+    entry an observed zero ('zero', beta in {1, 2}), without the reconstruction: a 0-dim float64 device tensor."""
+    T, fs = _prepare_sparse(T, factors, beta, unstored)
+    return _sparse_loss(T, fs, float(beta), unstored, stage)[0]
+
+
 class NTF(nn.Module):
     """Non-negative CP factorisation ``V (I, J, K) ~ sum_r A[:, r] x B[:, r] x C[:, r]``.
 
@@ -191,17 +397,24 @@ class NTF(nn.Module):
         return torch.einsum('ir,jr,kr->ijk', A, B, Cf)
 
     def fit(self, V: Tensor, beta: float = 1, tol: float = 1e-4, max_iter: int = 200, verbose: bool = False, alpha: float = 0,
-            l1_ratio: float = 0, weights=None) -> int:
+            l1_ratio: float = 0, weights=None, unstored: Optional[str] = None) -> int:
         """Fit the trainable factors to ``V`` by multiplicative updates: one iteration updates modes 0, 1, 2 in that order.
         Loss checkpoints and the stop rule are ``NMF.fit``'s (after iterations 9, 19, ...: stop when
         ``(previous - loss) / loss_init < tol``); returns the number of iterations.  ``weights``: None, or a dense tensor of
         ``V``'s shape (bool, integer or floating, >= 0); entries of weight 0 count for nothing whatever ``V`` holds there.
-        ``alpha`` / ``l1_ratio`` regularise as in ``NMF.fit``.  Rank <= 256, exact fp32, device tensors only."""
+        ``alpha`` / ``l1_ratio`` regularise as in ``NMF.fit``.  Rank <= 256, exact fp32, device tensors only.
+
+        A 3-D sparse COO ``V`` (or a ``SparseNtfTarget``) is fitted over its stored entries when ``unstored`` says how to
+        read the others: ``'missing'`` -- unknown (ratings, unsampled triples; every beta, beta <= 0 needs positive stored
+        values), ``'zero'`` -- observed zeros (count tensors; beta in {1, 2}).  Nothing of the dense tensor's size exists."""
+        if unstored is not None:
+            return self._fit_sparse(V, float(beta), tol, max_iter, verbose, alpha, l1_ratio, weights, unstored)
         if not isinstance(V, Tensor):
             raise ValueError(f'NTF.fit takes a dense 3-D tensor, got {type(V).__name__}')
         if V.is_sparse:
             raise NotImplementedError("NTF.fit takes a dense tensor; missing entries are given by weights=, and a sparse "
-                                      "matrix is fitted over its stored entries by NMF.fit(..., unstored='missing')")
+                                      "matrix is fitted over its stored entries by NMF.fit(..., unstored='missing').  A "
+                                      "sparse 3-D tensor needs the keyword too: NTF.fit(V, unstored='missing' | 'zero')")
         if V.dim() != 3:
             raise NotImplementedError(f'NTF factorises tensors of order 3, got order {V.dim()}')
         if tuple(V.shape) != tuple(f.shape[0] for f in self.factors):
@@ -258,6 +471,73 @@ class NTF(nn.Module):
                 for mode, f in enumerate(self.factors):
                     if f.requires_grad:
                         _ntf_call(T, fs, mode, beta, step=step, _ws=ws)
+                if n_iter % 10 == 9:
+                    loss = _sqrt2(divergence())
+                    if pbar is not None:
+                        pbar.set_postfix(loss=loss)
+                        pbar.update(10)
+                    if (previous - loss) / loss_init < tol:      # nmf.py:402-407
+                        break
+                    previous = loss
+        finally:
+            if pbar is not None:
+                pbar.close()
+        return n_iter + 1
+
+    def _fit_sparse(self, V, beta, tol, max_iter, verbose, alpha, l1_ratio, weights, unstored) -> int:
+        """``fit`` on a sparse target: the refusals in their order, then ``fit``'s loop on ``nmfmu_sp_ntf_step``."""
+        if unstored not in ('zero', 'missing'):
+            raise ValueError(f"unstored must be 'zero' or 'missing', got {unstored!r}")
+        if not isinstance(V, SparseNtfTarget) and not (isinstance(V, Tensor) and V.is_sparse):
+            raise ValueError('unstored= reads a sparse COO target (or a SparseNtfTarget); a dense tensor stores every entry')
+        _check_sparse(tuple(V.shape), list(self.factors), beta, unstored, weights)
+        _require_device(V, 'NTF.fit')
+        for f in self.factors:
+            _require_device(f, 'NTF.fit')
+        if any(f.dtype != torch.float32 for f in self.factors):
+            # fitted on fp32 working copies and stored back in the module's dtype, as the dense fit does
+            if not all(f.dtype.is_floating_point for f in self.factors):
+                raise NotImplementedError(f'factors must be floating point; got {[f.dtype for f in self.factors]}')
+            keep = [f.data for f in self.factors]
+            for f in self.factors:
+                f.data = f.data.float().contiguous()
+            try:
+                return self._fit_sparse(V, beta, tol, max_iter, verbose, alpha, l1_ratio, weights, unstored)
+            finally:
+                for f, k in zip(self.factors, keep):
+                    f32, f.data = f.data, k
+                    f.data.copy_(f32)
+        step = (float(alpha * l1_ratio), float(alpha * (1 - l1_ratio)), mu_gamma(beta))     # nmf.py:348-349
+        T = V if isinstance(V, SparseNtfTarget) else SparseNtfTarget(V)
+        assert not T.bad, "Target should be non-negative."
+        if T.has_zero and beta <= 0:
+            raise ValueError("When beta <= 0 and V contains zeros, the training process may diverge. "
+                             "Please add small values to V, or use a positive beta value.")
+        for f in self.factors:
+            if not f.data.is_contiguous():
+                f.data = f.data.contiguous()
+        fs = [f.data for f in self.factors]
+        lib = _capi.load()
+        r_pad = lib.nmfmu_pad_rank(self.rank)
+        ws = torch.empty(max(1, *(lib.nmfmu_sp_ntf_ws(m['n_ws'], r_pad) for m in T.modes)), dtype=torch.float32,
+                         device=T.device)
+        part = torch.empty((T.modes[0]['seg'].shape[0] + 3) // 4, dtype=torch.float64, device=T.device)
+        out = torch.zeros(1, dtype=torch.float64, device=T.device)
+
+        def divergence() -> float:
+            return float(_sparse_loss(T, fs, beta, unstored, part=part, out=out).item())
+
+        loss_init = previous = _sqrt2(divergence())      # nmf.py:355-363
+        pbar = None
+        if verbose:
+            from tqdm import tqdm
+            pbar = tqdm(total=max_iter)
+        n_iter = -1
+        try:
+            for n_iter in range(max_iter):
+                for mode, f in enumerate(self.factors):
+                    if f.requires_grad:
+                        _sparse_call(T, fs, mode, beta, unstored, step=step, _ws=ws)
                 if n_iter % 10 == 9:
                     loss = _sqrt2(divergence())
                     if pbar is not None:
