@@ -96,6 +96,9 @@ extern "C" {
                                   nmfmu_ntf_terms / nmfmu_ntf_step / nmfmu_ntf_loss / nmfmu_ntf_ws / nmfmu_ntf_nsplit /
                                   nmfmu_ntf_loss_parts (ntf.NTF: non-negative CP factorisation of a 3-way tensor walked in
                                   place, Khatri-Rao rows formed in LDS; added at ABI 10, additive);
+                                  nmfmu_ntf_short_terms / nmfmu_ntf_short_step / nmfmu_ntf_short_ws / nmfmu_ntf_short_nsplit /
+                                  nmfmu_ntf_tile (the same half-step on a 32-row tile for short owner modes, and the library's
+                                  choice between the two tiles; added at ABI 10, additive);
                                   nmfmu_sp_ntf_terms / nmfmu_sp_ntf_step / nmfmu_sp_ntf_loss / nmfmu_sp_ntf_ws /
                                   nmfmu_sp_ntf_lds_rows (ntf.NTF on sparse-COO tensors: the fit over the stored entries,
                                   unstored = 'missing' | 'zero'; added at ABI 10, additive);
@@ -998,6 +1001,26 @@ int nmfmu_ntf_step(const float* V, const float* M, int I, int J, int K, int mode
 int nmfmu_ntf_loss_parts(int I, int J, int K);
 int nmfmu_ntf_loss(const float* V, const float* M, int I, int J, int K, const float* A, const float* B, const float* C, int rank,
                    float beta, double v_term, double* part, double* out, void* stream);
+
+/* The same half-step on the SHORT tile (csrc/nmfmu_ntf_short.hip): a workgroup owns 32 owner rows x a rank tile x one part and
+ * its WS waves (4 / 4 / 2 / 1 at r_pad 32 / 64 / 128 / 256) lie along the contraction, so a mode of <= 32 rows keeps every wave
+ * on real rows.  Arithmetic, arguments, checks, error codes, slab layout and the bitwise-repeatable contract are those of
+ * nmfmu_ntf_terms / nmfmu_ntf_step; correct for any number of rows.  The parts are whole stages of 32 WS steps:
+ * nmfmu_ntf_short_nsplit(...) is 512 workgroups' worth over (rows / 32) x rank tiles, parts of >= 4 stages; ws holds
+ * nmfmu_ntf_short_ws(...) floats.  The sums run in another order than the wide tile's, so the two agree within their bounds,
+ * not bit for bit.
+ *   nmfmu_ntf_tile : the library's choice for a mode, 0 = the 128-row tile (nmfmu_ntf_*), 1 = the short tile: rows <= 32 and
+ *                    contraction >= 65536 (measured: below that the wide tile is as fast or faster, both near launch
+ *                    latency).  Host code only; rows, contraction or r_pad <= 0: NMFMU_ERR_ARG. */
+int nmfmu_ntf_short_nsplit(int rows, int contraction, int r_pad);
+int64_t nmfmu_ntf_short_ws(int rows, int contraction, int r_pad, int nsplit);
+int nmfmu_ntf_short_terms(const float* V, const float* M, int I, int J, int K, int mode, const float* owner, const float* pa,
+                          const float* pb, int rank, int r_pad, float beta, int nsplit, float* ws, float* num, float* den,
+                          void* stream);
+int nmfmu_ntf_short_step(const float* V, const float* M, int I, int J, int K, int mode, float* owner, const float* pa,
+                         const float* pb, int rank, int r_pad, float beta, float l1, float l2, float gamma, int nsplit, float* ws,
+                         void* stream);
+int nmfmu_ntf_tile(int rows, int contraction, int r_pad);
 
 /* ---- NTF on a sparse 3-way target: the fit over the STORED entries (additive entries) -----------------------------------------
  * Per mode the target is held sorted by (owner index, a, b), a < b the other two modes: seg / multi are the segment lists of

@@ -37,14 +37,11 @@
 #include "../../include/nmfmu.h"
 #include "nmfmu_fused.h"
 #include "nmfmu_mu_terms.h"
+#include "nmfmu_ntf_host.h"
 #include "nmfmu_sparse_common.h"
 #include "nmfmu_wmu_tile.h"
 
 namespace nmfmu {
-
-constexpr int kNtfTargetWgs = 512;          // two workgroups on each of the 256 CUs
-constexpr int kNtfMaxContraction = 1 << 30; // flat steps are ints; parts * part_len stays below 2^31
-constexpr int kNtfMaxParts = 65535;         // the parts are grid.z
 
 inline int ntf_auto_split(int rows, int contraction, int r_pad) {
   const int64_t tiles = (int64_t)((rows + kWmRows - 1) / kWmRows) * ((r_pad + 127) / 128);
@@ -297,35 +294,16 @@ __global__ void __launch_bounds__(256) ntf_loss_kernel(const float* __restrict__
   store_lane_totals(tot, red, part);
 }
 
+void ntf_finish_launch(int fblocks, const float* ws, int parts, int rows, int rank, int r_pad, float* owner, float* num,
+                       float* den, int step, MaskedApply ap, hipStream_t st) {
+  hipLaunchKernelGGL(ntf_finish_kernel, dim3(fblocks), dim3(256), 0, st, ws, parts, rows, rank, r_pad, owner, num, den, step, ap);
+}
+
 }  // namespace nmfmu
 
 using namespace nmfmu;
 
 namespace {
-// a half-step's view of the tensor: owner rows, the two contraction dimensions, the walk and its strides
-struct NtfMode {
-  int rows, nA, nB, outer;
-  int64_t sO, sA;
-};
-
-NtfMode ntf_mode(int I, int J, int K, int mode) {
-  const int64_t JK = (int64_t)J * K;
-  if (mode == 0) return NtfMode{I, J, K, 0, JK, K};
-  if (mode == 1) return NtfMode{J, I, K, 0, K, JK};
-  return NtfMode{K, I, J, 1, 1, K};
-}
-
-// NMFMU_OK or the answer the entries give before any device work
-int ntf_check(const void* V, int I, int J, int K, int mode, const void* owner, const void* pa, const void* pb, int rank,
-              int r_pad, bool has_r_pad, int nsplit = 0) {
-  if (const int rc = wmu_check(pb && I > 0 && J > 0 && K > 0 && mode >= 0 && mode <= 2, V, owner, pa, rank, r_pad, has_r_pad))
-    return rc;
-  const NtfMode md = ntf_mode(I, J, K, mode);
-  if ((int64_t)md.nA * md.nB > kNtfMaxContraction) return NMFMU_ERR_UNSUPPORTED;
-  if (has_r_pad && ntf_split(md.rows, md.nA * md.nB, r_pad, nsplit) > kNtfMaxParts) return NMFMU_ERR_UNSUPPORTED;   // a forced split
-  return NMFMU_OK;
-}
-
 int ntf_launch(const float* V, const float* M, int I, int J, int K, int mode, float* owner, const float* pa, const float* pb,
                int rank, int r_pad, float beta, int nsplit, float* ws, float* num, float* den, int step, MaskedApply ap,
                hipStream_t st) {
@@ -345,9 +323,7 @@ int ntf_launch(const float* V, const float* M, int I, int J, int K, int mode, fl
                            owner, pa, pb, rank, beta, part_len, sl.on, sl.od, sl.pstride);
     });
   });
-  if (!sl.direct)
-    hipLaunchKernelGGL(ntf_finish_kernel, dim3(sl.fblocks), dim3(256), 0, st, ws, parts, rows, rank, r_pad, owner, num, den,
-                       step, ap);
+  if (!sl.direct) ntf_finish_launch(sl.fblocks, ws, parts, rows, rank, r_pad, owner, num, den, step, ap, st);
   return (int)hipGetLastError();
 }
 
@@ -370,7 +346,7 @@ int nmfmu_ntf_terms(const float* V, const float* M, int I, int J, int K, int mod
                     const float* pb, int rank, int r_pad, float beta, int nsplit, float* ws, float* num, float* den,
                     void* stream) {
   if (!ws || !num || !den || nsplit < 0) return NMFMU_ERR_ARG;
-  if (const int rc = ntf_check(V, I, J, K, mode, owner, pa, pb, rank, r_pad, true, nsplit)) return rc;
+  if (const int rc = ntf_check(V, I, J, K, mode, owner, pa, pb, rank, r_pad, true, nsplit, ntf_split)) return rc;
   return ntf_launch(V, M, I, J, K, mode, const_cast<float*>(owner), pa, pb, rank, r_pad, beta, nsplit, ws, num, den, 0,
                     MaskedApply{0.f, 0.f, 1.f}, S(stream));
 }
@@ -378,7 +354,7 @@ int nmfmu_ntf_terms(const float* V, const float* M, int I, int J, int K, int mod
 int nmfmu_ntf_step(const float* V, const float* M, int I, int J, int K, int mode, float* owner, const float* pa, const float* pb,
                    int rank, int r_pad, float beta, float l1, float l2, float gamma, int nsplit, float* ws, void* stream) {
   if (!ws || owner == pa || owner == pb || nsplit < 0) return NMFMU_ERR_ARG;
-  if (const int rc = ntf_check(V, I, J, K, mode, owner, pa, pb, rank, r_pad, true, nsplit)) return rc;
+  if (const int rc = ntf_check(V, I, J, K, mode, owner, pa, pb, rank, r_pad, true, nsplit, ntf_split)) return rc;
   return ntf_launch(V, M, I, J, K, mode, owner, pa, pb, rank, r_pad, beta, nsplit, ws, nullptr, nullptr, 1,
                     MaskedApply{l1, l2, gamma}, S(stream));
 }
@@ -392,7 +368,7 @@ int nmfmu_ntf_loss_parts(int I, int J, int K) {
 int nmfmu_ntf_loss(const float* V, const float* M, int I, int J, int K, const float* A, const float* B, const float* C, int rank,
                    float beta, double v_term, double* part, double* out, void* stream) {
   if (!part || !out || !A) return NMFMU_ERR_ARG;
-  if (const int rc = ntf_check(V, I, J, K, 0, A, B, C, rank, 0, false)) return rc;
+  if (const int rc = ntf_check(V, I, J, K, 0, A, B, C, rank, 0, false, 0, ntf_split)) return rc;
   const int JK = J * K;
   const int nparts = ntf_loss_split(I, JK), part_len = wmu_part_len(JK, nparts);
   const int nblk = (I + kWmRows - 1) / kWmRows * nparts;

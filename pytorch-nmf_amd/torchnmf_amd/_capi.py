@@ -193,6 +193,15 @@ SIGNATURES = {
                                   C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'nmfmu_ntf_step': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
+    'nmfmu_ntf_short_nsplit': (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    'nmfmu_ntf_short_ws': (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    'nmfmu_ntf_short_terms': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
+    'nmfmu_ntf_short_step': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int,
+                                       C.c_void_p, C.c_void_p]),
+    'nmfmu_ntf_tile': (C.c_int, [C.c_int, C.c_int, C.c_int]),
     'nmfmu_ntf_loss_parts': (C.c_int, [C.c_int, C.c_int, C.c_int]),
     'nmfmu_ntf_loss': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                  C.c_float, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),

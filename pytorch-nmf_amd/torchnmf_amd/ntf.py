@@ -90,11 +90,27 @@ class NtfTarget:
         return self._v_term[beta]
 
 
+def _check_tile(tile) -> None:
+    if tile not in (None, 'wide', 'short'):
+        raise ValueError(f"tile must be None, 'wide' or 'short', got {tile!r}")
+
+
+def _tile_entries(lib, tile, rows: int, contraction: int, r_pad: int):
+    """(workspace rule, terms entry, step entry, the step's name) of the mode's tile: the 128-row tile of csrc/nmfmu_ntf.hip
+    or the 32-row tile of csrc/nmfmu_ntf_short.hip.  ``tile`` None: the library's choice, ``nmfmu_ntf_tile``."""
+    short = lib.nmfmu_ntf_tile(rows, contraction, r_pad) == 1 if tile is None else tile == 'short'
+    if short:
+        return lib.nmfmu_ntf_short_ws, lib.nmfmu_ntf_short_terms, lib.nmfmu_ntf_short_step, 'nmfmu_ntf_short'
+    return lib.nmfmu_ntf_ws, lib.nmfmu_ntf_terms, lib.nmfmu_ntf_step, 'nmfmu_ntf'
+
+
 def _ntf_call(T: NtfTarget, factors: Sequence[Tensor], mode: int, beta: float, step=None, nsplit: int = 0, _fill=None,
-              _ws=None):
+              _ws=None, tile=None):
     """``nmfmu_ntf_terms`` (``step`` None: returns (num, den), fp32 ``[dim_mode, r_pad]``) or ``nmfmu_ntf_step`` (``step`` =
     (l1, l2, gamma): ``factors[mode]`` updated in place).  ``factors``: three contiguous fp32 ``[dim_n, R]``.  Enqueued only.
-    ``_fill``: tests pre-fill the outputs and the workspace with it."""
+    ``_fill``: tests pre-fill the outputs and the workspace with it.  ``tile``: None (the library's choice for this mode),
+    'wide' or 'short' -- the ``nmfmu_ntf_short_*`` entries."""
+    _check_tile(tile)
     lib = _capi.load()
     I, J, K = T.shape
     owner = factors[mode]
@@ -103,7 +119,8 @@ def _ntf_call(T: NtfTarget, factors: Sequence[Tensor], mode: int, beta: float, s
     assert tuple(f.shape for f in factors) == ((I, R), (J, R), (K, R))
     r_pad = lib.nmfmu_pad_rank(R)
     contraction = I * J * K // rows
-    n_float = lib.nmfmu_ntf_ws(rows, contraction, r_pad, nsplit)
+    ws_rule, terms_entry, step_entry, name = _tile_entries(lib, tile, rows, contraction, r_pad)
+    n_float = ws_rule(rows, contraction, r_pad, nsplit)
     ws = _ws if _ws is not None else torch.empty(max(n_float, 1), dtype=torch.float32, device=T.device)
     assert ws.numel() >= n_float
     if _fill is not None:
@@ -112,15 +129,14 @@ def _ntf_call(T: NtfTarget, factors: Sequence[Tensor], mode: int, beta: float, s
             pb.data_ptr(), R, r_pad, beta)
     if step is not None:
         l1, l2, gamma = step
-        _capi.check(lib.nmfmu_ntf_step(*head, l1, l2, gamma, nsplit, ws.data_ptr(), _stream()), 'nmfmu_ntf_step')
+        _capi.check(step_entry(*head, l1, l2, gamma, nsplit, ws.data_ptr(), _stream()), name + '_step')
         return None
     num = torch.empty(rows, r_pad, dtype=torch.float32, device=T.device)
     den = torch.empty(rows, r_pad, dtype=torch.float32, device=T.device)
     if _fill is not None:
         num.fill_(_fill)
         den.fill_(_fill)
-    _capi.check(lib.nmfmu_ntf_terms(*head, nsplit, ws.data_ptr(), num.data_ptr(), den.data_ptr(), _stream()),
-                'nmfmu_ntf_terms')
+    _capi.check(terms_entry(*head, nsplit, ws.data_ptr(), num.data_ptr(), den.data_ptr(), _stream()), name + '_terms')
     return num, den
 
 
@@ -148,12 +164,14 @@ def _prepare(V, weights, factors):
     return T, [f.detach().float().contiguous() for f in factors]
 
 
-def ntf_terms(V, weights, factors: Sequence[Tensor], mode: int, beta: float, nsplit: int = 0):
+def ntf_terms(V, weights, factors: Sequence[Tensor], mode: int, beta: float, nsplit: int = 0, tile=None):
     """``(num, den)`` of the half-step of ``mode`` (0, 1 or 2), fp32 ``[dim_mode, r_pad]`` with zeros in the padded rank
     columns; ``den - num`` is the gradient of the loss with respect to ``factors[mode]``.  ``V``: a dense ``[I, J, K]`` device
-    tensor with ``weights`` of its shape or None, or an ``NtfTarget`` prepared once."""
+    tensor with ``weights`` of its shape or None, or an ``NtfTarget`` prepared once.  ``tile``: None -- the library chooses
+    (the 32-row tile for a mode of at most 32 rows over a long contraction, else the 128-row tile) -- or 'wide' / 'short'."""
+    _check_tile(tile)
     T, fs = _prepare(V, weights, factors)
-    return _ntf_call(T, fs, int(mode), float(beta), nsplit=nsplit)
+    return _ntf_call(T, fs, int(mode), float(beta), nsplit=nsplit, tile=tile)
 
 
 def ntf_loss(V, weights, factors: Sequence[Tensor], beta: float) -> Tensor:
@@ -397,17 +415,22 @@ class NTF(nn.Module):
         return torch.einsum('ir,jr,kr->ijk', A, B, Cf)
 
     def fit(self, V: Tensor, beta: float = 1, tol: float = 1e-4, max_iter: int = 200, verbose: bool = False, alpha: float = 0,
-            l1_ratio: float = 0, weights=None, unstored: Optional[str] = None) -> int:
+            l1_ratio: float = 0, weights=None, unstored: Optional[str] = None, tile: Optional[str] = None) -> int:
         """Fit the trainable factors to ``V`` by multiplicative updates: one iteration updates modes 0, 1, 2 in that order.
         Loss checkpoints and the stop rule are ``NMF.fit``'s (after iterations 9, 19, ...: stop when
         ``(previous - loss) / loss_init < tol``); returns the number of iterations.  ``weights``: None, or a dense tensor of
         ``V``'s shape (bool, integer or floating, >= 0); entries of weight 0 count for nothing whatever ``V`` holds there.
-        ``alpha`` / ``l1_ratio`` regularise as in ``NMF.fit``.  Rank <= 256, exact fp32, device tensors only.
+        ``alpha`` / ``l1_ratio`` regularise as in ``NMF.fit``.  Rank <= 256, exact fp32, device tensors only.  ``tile``: None --
+        per mode the library's choice between the 128-row tile and the 32-row tile for short modes (at most 32 rows over a
+        contraction of at least 65536) -- or 'wide' / 'short' for every mode; dense targets only.
 
         A 3-D sparse COO ``V`` (or a ``SparseNtfTarget``) is fitted over its stored entries when ``unstored`` says how to
         read the others: ``'missing'`` -- unknown (ratings, unsampled triples; every beta, beta <= 0 needs positive stored
         values), ``'zero'`` -- observed zeros (count tensors; beta in {1, 2}).  Nothing of the dense tensor's size exists."""
+        _check_tile(tile)
         if unstored is not None:
+            if tile is not None:
+                raise NotImplementedError('tile= chooses between the dense kernels; a sparse target has one kernel')
             return self._fit_sparse(V, float(beta), tol, max_iter, verbose, alpha, l1_ratio, weights, unstored)
         if not isinstance(V, Tensor):
             raise ValueError(f'NTF.fit takes a dense 3-D tensor, got {type(V).__name__}')
@@ -434,7 +457,7 @@ class NTF(nn.Module):
             for f in self.factors:
                 f.data = f.data.float().contiguous()
             try:
-                return self.fit(V, beta, tol, max_iter, verbose, alpha, l1_ratio, weights)
+                return self.fit(V, beta, tol, max_iter, verbose, alpha, l1_ratio, weights, tile=tile)
             finally:
                 for f, k in zip(self.factors, keep):
                     f32, f.data = f.data, k
@@ -452,8 +475,8 @@ class NTF(nn.Module):
         fs = [f.data for f in self.factors]
         lib, (I, J, K) = _capi.load(), T.shape
         r_pad = lib.nmfmu_pad_rank(self.rank)
-        ws = torch.empty(max(lib.nmfmu_ntf_ws(d, I * J * K // d, r_pad, 0) for d in T.shape), dtype=torch.float32,
-                         device=T.device)
+        ws = torch.empty(max(_tile_entries(lib, tile, d, I * J * K // d, r_pad)[0](d, I * J * K // d, r_pad, 0) for d in T.shape),
+                         dtype=torch.float32, device=T.device)      # per mode by the tile that mode takes
         part = torch.empty(lib.nmfmu_ntf_loss_parts(I, J, K), dtype=torch.float64, device=T.device)
         out = torch.zeros(1, dtype=torch.float64, device=T.device)
 
@@ -470,7 +493,7 @@ class NTF(nn.Module):
             for n_iter in range(max_iter):
                 for mode, f in enumerate(self.factors):
                     if f.requires_grad:
-                        _ntf_call(T, fs, mode, beta, step=step, _ws=ws)
+                        _ntf_call(T, fs, mode, beta, step=step, _ws=ws, tile=tile)
                 if n_iter % 10 == 9:
                     loss = _sqrt2(divergence())
                     if pbar is not None:

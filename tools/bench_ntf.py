@@ -16,6 +16,16 @@ before every call.  ``fraction_of_hbm`` counts V (and M) once against 8 TB/s, ``
 den) against 157.3 TFLOP/s, both over the whole ntf step; ``peak_bytes`` is torch's high-water mark of the route above what
 V, M and the factors hold.
 
+``--short`` times the 32-row tile instead (``nmfmu_ntf_short_step``, csrc/nmfmu_ntf_short.hip) on the short owner modes it is
+for, beside the forced 128-row tile and the torch loop, and sweeps the contraction length at 8 rows for the automatic rule of
+``nmfmu_ntf_tile``; same method, same rounds.  Its output goes to profiles/ntf_short.json:
+
+    python tools/bench_ntf.py --short
+
+  short   one nmfmu_ntf_short_step (the 32-row tile + the finishing kernel)
+  wide    one nmfmu_ntf_step (the 128-row tile) on the same mode
+  torch   the fp32 torch loop above (the workloads only, not the sweep)
+
 Every workload runs in a child process of its own under its own time limit; the first that fails ends the run (no retries).
 """
 import argparse
@@ -29,6 +39,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'pytorch-nmf_amd'))
 
 WORKLOADS = {'8x1025x8192_r32': ((8, 1025, 8192), 32), '512x512x512_r64': ((512, 512, 512), 64)}
+# --short: (shape, rank) of tensors whose mode 0 is short; the sweep is 8 x (c / 128) x 128 at every padded rank
+SHORT_WORKLOADS = {'8x1025x8192_r32': ((8, 1025, 8192), 32), '8x1025x8192_r128': ((8, 1025, 8192), 128),
+                   '2x1025x8192_r32': ((2, 1025, 8192), 32), '24x4096x4096_r64': ((24, 4096, 4096), 64)}
+SWEEP = 'sweep_8_rows'
+SWEEP_RANKS, SWEEP_LOG2 = (32, 64, 128, 256), range(10, 21)
 BETAS = (1.0, 0.5)
 WARMUP, REPEATS = 2, 10
 HBM_PEAK, FP32_MFMA_PEAK = 8e12, 157.3e12
@@ -151,20 +166,99 @@ def run_item(name):
     return dict(item=name, device=torch.cuda.get_device_name(0), rows=rows_out)
 
 
+def run_short_item(name):
+    """Mode 0 of one --short workload (or the sweep): the routes in turn, round by round, as run_item does."""
+    import torch
+    from torchnmf_amd import _capi
+    from torchnmf_amd.constants import eps
+    from torchnmf_amd.engine import mu_gamma
+    dev, lib = torch.device('cuda:0'), _capi.load()
+    stream = torch.cuda.current_stream().cuda_stream
+    g = torch.Generator(device=dev).manual_seed(3)
+    sweep = name == SWEEP
+    cases = ([((8, (1 << k) // 128, 128), R) for R in SWEEP_RANKS for k in SWEEP_LOG2] if sweep else [SHORT_WORKLOADS[name]])
+    rows_out = []
+    for shape, R in cases:
+        I, J, K = shape
+        start = [torch.rand(d, R, generator=g, device=dev) + 0.25 for d in shape]
+        V = torch.rand(shape, generator=g, device=dev) + 0.1
+        Mw = (torch.rand(shape, generator=g, device=dev) * 3.75 + 0.25) * (torch.rand(shape, generator=g, device=dev) > 0.3)
+        r_pad, contraction = lib.nmfmu_pad_rank(R), J * K
+        ws = torch.empty(max(lib.nmfmu_ntf_ws(I, contraction, r_pad, 0), lib.nmfmu_ntf_short_ws(I, contraction, r_pad, 0)),
+                         dtype=torch.float32, device=dev)
+        for weighted, beta in (((False, 1.0), (True, 0.5)) if sweep else [(w, b) for w in (False, True) for b in BETAS]):
+            M = Mw if weighted else None
+            step = (0.0, 0.0, mu_gamma(beta))
+            fs = [f.clone() for f in start]
+
+            def restore():
+                fs[0].copy_(start[0])
+
+            def entry(fn, what):
+                def call():
+                    _capi.check(fn(V.data_ptr(), None if M is None else M.data_ptr(), I, J, K, 0, fs[0].data_ptr(), fs[1].data_ptr(),
+                                   fs[2].data_ptr(), R, r_pad, beta, *step, 0, ws.data_ptr(), stream), what)
+                return call
+
+            def torch_step():
+                y = torch.einsum('ir,jr,kr->ijk', *fs)
+                if beta == 1.0:
+                    gn, gp = V / (y + eps), torch.ones_like(y)
+                else:
+                    p2 = (y + eps).pow(beta - 2)
+                    gn, gp = p2 * V, p2 * (y + eps)
+                if weighted:
+                    gn, gp = torch.where(Mw > 0, Mw * gn, 0.0), torch.where(Mw > 0, Mw * gp, 0.0)
+                num, den = torch.einsum('ijk,jr,kr->ir', gn, fs[1], fs[2]), torch.einsum('ijk,jr,kr->ir', gp, fs[1], fs[2])
+                fs[0].mul_(((num.clamp_min(0) + eps) / (den.clamp_min(0) + eps)).pow(step[2]))
+            routes = dict(short=entry(lib.nmfmu_ntf_short_step, 'nmfmu_ntf_short_step'), wide=entry(lib.nmfmu_ntf_step, 'nmfmu_ntf_step'))
+            if not sweep:
+                routes['torch'] = torch_step
+            result = {}
+            for k, call in routes.items():
+                for _ in range(WARMUP):
+                    one(call, restore)
+                result[k] = fs[0].clone()
+            ts = {k: [] for k in routes}
+            for _ in range(REPEATS):                               # the routes in turn, round by round
+                for k, call in routes.items():
+                    ts[k].append(one(call, restore))
+            ms = statistics.median(ts['short']) * 1e-3
+            row = dict(workload=name, shape=list(shape), rank=R, r_pad=r_pad, beta=beta, weighted=weighted, mode=0, rows=I,
+                       contraction=contraction, auto_tile=lib.nmfmu_ntf_tile(I, contraction, r_pad),
+                       short=dict(stats(ts['short']), parts=lib.nmfmu_ntf_short_nsplit(I, contraction, r_pad),
+                                  fraction_of_hbm=4.0 * I * J * K * (2 if weighted else 1) / ms / HBM_PEAK,
+                                  fraction_of_fp32_mfma_peak=6.0 * I * J * K * R / ms / FP32_MFMA_PEAK),
+                       wide=dict(stats(ts['wide']), parts=lib.nmfmu_ntf_nsplit(I, contraction, r_pad)),
+                       max_rel_diff_short_to_wide=float(((result['short'] - result['wide']).abs() / result['wide']).max()))
+            if not sweep:
+                row['torch'] = dict(stats(ts['torch']),
+                                    max_rel_diff_to_short=float(((result['torch'] - result['short']).abs() / result['short']).max()))
+            rows_out.append(row)
+            print(json.dumps(row), flush=True)
+        del ws, V, Mw
+    return dict(item=name, device=torch.cuda.get_device_name(0), rows=rows_out)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'ntf.json'))
-    ap.add_argument('--item', choices=list(WORKLOADS), help='run ONE workload in this process (the driver calls this)')
+    ap.add_argument('--short', action='store_true', help='the 32-row tile on short modes and the sweep for nmfmu_ntf_tile')
+    ap.add_argument('--out', help='default: profiles/ntf.json, with --short profiles/ntf_short.json')
+    ap.add_argument('--item', help='run ONE workload in this process (the driver calls this)')
     a = ap.parse_args()
+    items = list(SHORT_WORKLOADS) + [SWEEP] if a.short else list(WORKLOADS)
+    a.out = a.out or os.path.join(ROOT, 'profiles', 'ntf_short.json' if a.short else 'ntf.json')
     if a.item:
-        print('ITEM_RESULT ' + json.dumps(run_item(a.item)), flush=True)
+        assert a.item in items, items
+        print('ITEM_RESULT ' + json.dumps((run_short_item if a.short else run_item)(a.item)), flush=True)
         return 0
     res = dict(tool='tools/bench_ntf.py', betas=list(BETAS), warmup=WARMUP, repeats=REPEATS, hbm_peak=HBM_PEAK,
                fp32_mfma_peak=FP32_MFMA_PEAK, flop_per_half_step='6 I J K R', rows=[], failed=None)
     rc = 0
-    for item in WORKLOADS:          # chained: the first failure ends the run, nothing is tried again
+    for item in items:              # chained: the first failure ends the run, nothing is tried again
         try:
-            p = subprocess.run([sys.executable, os.path.abspath(__file__), '--item', item], capture_output=True, text=True,
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), '--item', item] + ['--short'] * a.short,
+                               capture_output=True, text=True,
                                timeout=ITEM_LIMIT_S)
         except subprocess.TimeoutExpired:
             res['failed'], rc = dict(item=item, why=f'time limit of {ITEM_LIMIT_S} s'), 124
