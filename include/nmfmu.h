@@ -102,6 +102,8 @@ extern "C" {
                                   nmfmu_sp_ntf_terms / nmfmu_sp_ntf_step / nmfmu_sp_ntf_loss / nmfmu_sp_ntf_ws /
                                   nmfmu_sp_ntf_lds_rows (ntf.NTF on sparse-COO tensors: the fit over the stored entries,
                                   unstored = 'missing' | 'zero'; added at ABI 10, additive);
+                                  nmfmu_ntf_mttkrp / nmfmu_ntf_mttkrp_ws (the dense MTTKRP of a mode, the numerator of
+                                  ntf.NTF.fit(solver='hals'); added at ABI 10, additive);
                                10: nmfmu_plca_normalize / nmfmu_plca_z / nmfmu_plca3 take alpha as double (an argument changed its
                                   type: not additive).  The Dirichlet prior adds fp32(alpha - 1) with the subtraction in double,
                                   as the reference's in-place add does; fp32(alpha) - 1.f was off by 4.7e-5 relative at
@@ -1021,6 +1023,23 @@ int nmfmu_ntf_short_step(const float* V, const float* M, int I, int J, int K, in
                          const float* pb, int rank, int r_pad, float beta, float l1, float l2, float gamma, int nsplit, float* ws,
                          void* stream);
 int nmfmu_ntf_tile(int rows, int contraction, int r_pad);
+
+/* The dense MTTKRP of mode `mode` (csrc/nmfmu_ntf_mttkrp.hip), the numerator of a Frobenius half-step (ntf.NTF.fit(solver=
+ * 'hals'), ntf.ntf_mttkrp):  num[o][r] = sum_(a,b) V(o, a, b) fl32(pa[a][r] pb[b][r]),  modes, (a, b) and (pa, pb) as above, exact
+ * fp32 MFMA.  V goes from global memory straight into the A operand (never through LDS), the Khatri-Rao rows exist 32 at a time
+ * in LDS, a wave carries the whole padded rank (V is read once at every rank <= 256).  tile: 0 = wide, the four waves own 128
+ * consecutive owner rows; 1 = short, they own the same 32 rows and split each 128-step stage; either is correct for any
+ * number of rows.  The contraction is cut into parts of whole stages (32 steps wide, 128 short): nsplit == 0 takes as many as
+ * the fused tile of that arrangement (nmfmu_ntf_nsplit / nmfmu_ntf_short_nsplit), nsplit > 0 asks for that many.  ws:
+ * nmfmu_ntf_mttkrp_ws(owner rows, contraction, r_pad, nsplit, tile) floats, [part][owner rows][r_pad], plain stores, added in
+ * part order by a second kernel; num [owner rows][r_pad]: every element is written, the padded columns with 0.  A repeated call
+ * is bitwise identical whatever ws and num held; the two tiles agree within their bounds, not bit for bit.
+ * Null pointers, I, J, K, rank <= 0, mode not 0 / 1 / 2, r_pad != nmfmu_pad_rank(rank), nsplit < 0, tile not 0 / 1: NMFMU_ERR_ARG
+ * (nmfmu_ntf_mttkrp_ws: 0); rank > 256, a contraction of more than 2^30 steps or a forced nsplit that gives more than 65535
+ * parts: NMFMU_ERR_UNSUPPORTED -- both before any device work. */
+int64_t nmfmu_ntf_mttkrp_ws(int rows, int contraction, int r_pad, int nsplit, int tile);
+int nmfmu_ntf_mttkrp(const float* V, int I, int J, int K, int mode, const float* pa, const float* pb, int rank, int r_pad,
+                     int nsplit, int tile, float* ws, float* num, void* stream);
 
 /* ---- NTF on a sparse 3-way target: the fit over the STORED entries (additive entries) -----------------------------------------
  * Per mode the target is held sorted by (owner index, a, b), a < b the other two modes: seg / multi are the segment lists of

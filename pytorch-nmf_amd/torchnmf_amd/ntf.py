@@ -10,6 +10,11 @@ A 3-D sparse COO tensor is fitted over its STORED entries, ``fit(V_sparse, unsto
 holds one sorted copy per mode, one half-step is one ``nmfmu_sp_ntf_step`` call (csrc/nmfmu_sparse_ntf.hip: two panel rows
 gathered per stored entry and multiplied in registers; under 'zero' the denominator comes from column sums or Gram matrices
 of the factors).  ``sparse_ntf_terms`` / ``sparse_ntf_loss`` are the functional forms.
+
+``fit(beta=2, solver='hals')`` is HALS (Cichocki & Phan 2009), the coordinate descent of ``NMF.fit(solver='hals')`` on tensors: a
+half-step is the MTTKRP ``num[o] = sum_(a,b) V(o, a, b) Pa[a] o Pb[b]`` (``ntf_mttkrp``: csrc/nmfmu_ntf_mttkrp.hip, ``V`` read once,
+no reconstruction; on a sparse 'zero' target the numerator of ``nmfmu_sp_ntf_terms``), two Gram matrices and one
+``nmfmu_hals_sweep``.
 """
 from __future__ import annotations
 
@@ -21,11 +26,12 @@ from torch import Tensor, nn
 from . import _capi
 from . import sparse_autograd as SA
 from .constants import eps
+from .hals import _sweep
 from .engine import mu_gamma
 from .nmf import _require_device, _sqrt2
 from .wmu import check_weights
 
-__all__ = ['NTF', 'NtfTarget', 'ntf_terms', 'ntf_loss', 'SparseNtfTarget', 'sparse_ntf_terms', 'sparse_ntf_loss']
+__all__ = ['NTF', 'NtfTarget', 'ntf_terms', 'ntf_loss', 'SparseNtfTarget', 'sparse_ntf_terms', 'sparse_ntf_loss', 'ntf_mttkrp']
 
 MAX_RANK = 256
 MAX_CONTRACTION = 1 << 30      # csrc/nmfmu_ntf.hip: the flat contraction steps of a mode are ints
@@ -179,6 +185,57 @@ def ntf_loss(V, weights, factors: Sequence[Tensor], beta: float) -> Tensor:
     0-dim float64 device tensor.  Arguments as for ``ntf_terms``."""
     T, fs = _prepare(V, weights, factors)
     return _ntf_loss(T, fs, float(beta))[0]
+
+
+def _mttkrp_call(T: NtfTarget, factors: Sequence[Tensor], mode: int, nsplit: int = 0, tile=None, _fill=None, _ws=None,
+                 out=None) -> Tensor:
+    """``nmfmu_ntf_mttkrp`` of ``mode``: fp32 ``[dim_mode, r_pad]`` (``out`` or a new tensor).  ``factors``: three contiguous fp32
+    ``[dim_n, R]``.  Enqueued only.  ``tile``: None (``nmfmu_ntf_tile``'s choice for this mode), 'wide' or 'short'.  ``_fill``:
+    tests pre-fill the output and the workspace with it."""
+    _check_tile(tile)
+    lib = _capi.load()
+    I, J, K = T.shape
+    pa, pb = (f for n, f in enumerate(factors) if n != mode)
+    rows, R = factors[mode].shape
+    assert tuple(f.shape for f in factors) == ((I, R), (J, R), (K, R))
+    r_pad = lib.nmfmu_pad_rank(R)
+    contraction = I * J * K // rows
+    short = int(lib.nmfmu_ntf_tile(rows, contraction, r_pad) == 1 if tile is None else tile == 'short')
+    n_float = lib.nmfmu_ntf_mttkrp_ws(rows, contraction, r_pad, nsplit, short)
+    ws = _ws if _ws is not None else torch.empty(max(n_float, 1), dtype=torch.float32, device=T.device)
+    assert ws.numel() >= n_float
+    num = out if out is not None else torch.empty(rows, r_pad, dtype=torch.float32, device=T.device)
+    if _fill is not None:
+        ws.fill_(_fill)
+        num.fill_(_fill)
+    _capi.check(lib.nmfmu_ntf_mttkrp(T.V.data_ptr(), I, J, K, mode, pa.data_ptr(), pb.data_ptr(), R, r_pad, nsplit, short,
+                                     ws.data_ptr(), num.data_ptr(), _stream()), 'nmfmu_ntf_mttkrp')
+    return num
+
+
+class _Dense:
+    """What ``ntf_mttkrp`` needs of a dense tensor: contiguous fp32 ``V``, none of ``NtfTarget``'s scans."""
+
+    def __init__(self, V: Tensor):
+        self.V, self.shape, self.device = V.detach().float().contiguous(), tuple(V.shape), V.device
+
+
+def ntf_mttkrp(V, factors: Sequence[Tensor], mode: int, nsplit: int = 0, tile=None) -> Tensor:
+    """The MTTKRP of ``mode`` (0, 1 or 2): ``num[o, r] = sum_(a, b) V(o, a, b) Pa[a, r] Pb[b, r]`` over the other two modes, fp32
+    ``[dim_mode, r_pad]`` with zeros in the padded rank columns -- the numerator of a Frobenius half-step, one pass over ``V``
+    on the exact-fp32 MFMA kernel of csrc/nmfmu_ntf_mttkrp.hip.  ``V``: a dense ``[I, J, K]`` device tensor or an unweighted
+    ``NtfTarget``.  ``nsplit``: parts of the contraction (0: the library's rule).  ``tile``: as for ``ntf_terms``."""
+    _check_tile(tile)
+    if isinstance(V, NtfTarget):
+        if V.M is not None:
+            raise ValueError('ntf_mttkrp takes an unweighted target')
+    elif not isinstance(V, Tensor) or V.is_sparse or V.dim() != 3:
+        raise ValueError('ntf_mttkrp takes a dense 3-D tensor or an NtfTarget')
+    _check_shape(tuple(V.shape), factors[0].shape[1])
+    for t in (V.V if isinstance(V, NtfTarget) else V, *factors):
+        _require_device(t, 'NTF')
+    T = V if isinstance(V, NtfTarget) else _Dense(V)
+    return _mttkrp_call(T, [f.detach().float().contiguous() for f in factors], int(mode), nsplit=nsplit, tile=tile)
 
 
 # ---- sparse targets: the stored entries only ------------------------------------------------------------------------------------
@@ -381,6 +438,98 @@ def sparse_ntf_loss(T, factors: Sequence[Tensor], beta: float, unstored: str, st
     return _sparse_loss(T, fs, float(beta), unstored, stage)[0]
 
 
+class _HalsNtf:
+    """The half-steps and the loss of ``NTF.fit(beta=2, solver='hals')`` on the contiguous fp32 masters ``fs``, updated in place.
+
+    A half-step of mode n: the numerator (dense: ``nmfmu_ntf_mttkrp``; sparse 'zero': the ``num`` plane of
+    ``nmfmu_sp_ntf_terms`` at beta 2, the MTTKRP over the stored entries), ``G = Gram(Pa) o Gram(Pb)`` (symmetric) and one
+    ``nmfmu_hals_sweep`` on the owner.  Before the first half-step or loss the trainable factors are scaled once, as
+    ``HalsEngine`` does: ``a = <V, Y> / <Y, Y>`` with ``<V, Y> = sum num_0 o A`` and ``<Y, Y> = sum G_A o G_B o G_C`` (float64 dots),
+    each of the t trainable factors times ``a^(1/t)`` (skipped unless a is finite and positive), then clamped to >= eps.
+
+    The dense loss is ``1/2 |V|^2 - <V, Y> + 1/2 sum G_A o G_B o G_C`` in float64; ``<V, Y>`` is the dot of the last half-step's
+    numerator with its owner after the sweep (that numerator came from the two factors that have not changed since), so a
+    checkpoint costs no pass over ``V``.  Like ``HalsEngine``'s, the value loses digits when the fit is nearly exact: it is a
+    difference of numbers of the size of ``|V|^2``.  The sparse loss is ``_sparse_loss``."""
+
+    def __init__(self, T, fs, train, l1: float, l2: float, tile=None):
+        self.T, self.fs, self.train, self.l1, self.l2, self.tile = T, fs, [bool(t) for t in train], l1, l2, tile
+        self.sparse = isinstance(T, SparseNtfTarget)
+        self.lib = lib = _capi.load()
+        self.rank = R = fs[0].shape[1]
+        self._scaled, self._fresh = False, None      # _fresh: the mode whose numerator is num of the current factors
+        self.num = None
+        if self.sparse:
+            self.part = torch.empty((T.modes[0]['seg'].shape[0] + 3) // 4, dtype=torch.float64, device=T.device)
+            self.out = torch.zeros(1, dtype=torch.float64, device=T.device)
+            self.ws = torch.empty(max(1, *(lib.nmfmu_sp_ntf_ws(m['n_ws'], lib.nmfmu_pad_rank(R)) for m in T.modes)),
+                                  dtype=torch.float32, device=T.device)
+            return
+        I, J, K = T.shape
+        r_pad = lib.nmfmu_pad_rank(R)
+        n_ws = 1
+        for d in T.shape:      # per mode by the tile that mode takes
+            c = I * J * K // d
+            short = int(lib.nmfmu_ntf_tile(d, c, r_pad) == 1 if tile is None else tile == 'short')
+            n_ws = max(n_ws, lib.nmfmu_ntf_mttkrp_ws(d, c, r_pad, 0, short))
+        self.ws = torch.empty(n_ws, dtype=torch.float32, device=T.device)
+        self.bufs = [torch.empty(d, r_pad, dtype=torch.float32, device=T.device) for d in T.shape]
+        part = torch.empty(1024, dtype=torch.float64, device=T.device)
+        out = torch.zeros(2, dtype=torch.float64, device=T.device)
+        _capi.check(lib.nmfmu_norms(T.V.data_ptr(), T.V.numel(), part.data_ptr(), out.data_ptr(), _stream()), 'nmfmu_norms')
+        self.half_v2 = 0.5 * float(out[1].item())
+
+    def _numerator(self, mode: int) -> Tensor:
+        if self.sparse:
+            return _sparse_call(self.T, self.fs, mode, 2.0, 'zero', _ws=self.ws)[0]
+        return _mttkrp_call(self.T, self.fs, mode, tile=self.tile, _ws=self.ws, out=self.bufs[mode])
+
+    def _vy(self) -> Tensor:
+        """``<V, Y>`` of the current factors, a 0-dim float64 device tensor."""
+        if self._fresh is None:
+            self.num, self._fresh = self._numerator(0), 0
+        return (self.num[:, :self.rank].double() * self.fs[self._fresh].double()).sum()
+
+    def _yy(self) -> Tensor:
+        g = [_gram(self.lib, f).double() for f in self.fs]
+        return (g[0] * g[1] * g[2]).sum()
+
+    def _ensure_scaled(self) -> None:
+        if self._scaled:
+            return
+        self._scaled = True
+        t = sum(self.train)
+        if t:
+            vy, yy = float(self._vy().item()), float(self._yy().item())
+            a = vy / yy if yy != 0 else float('nan')
+            if a > 0 and a != float('inf'):
+                for f, on in zip(self.fs, self.train):
+                    if on:
+                        f.mul_(a ** (1.0 / t))
+                self._fresh = None
+        for f, on in zip(self.fs, self.train):
+            if on:
+                f.clamp_(min=eps)
+                self._fresh = None
+
+    def half_step(self, mode: int) -> None:
+        if not self.train[mode]:
+            return
+        self._ensure_scaled()
+        pa, pb = (f for n, f in enumerate(self.fs) if n != mode)
+        self.num = self._numerator(mode)
+        g = _gram(self.lib, pa) * _gram(self.lib, pb)
+        _sweep(self.fs[mode], self.num, self.num.stride(0), g, self.l1, self.l2)
+        self._fresh = mode
+
+    def divergence(self) -> float:
+        """The plain Frobenius loss (no regularisation terms).  One host sync."""
+        self._ensure_scaled()
+        if self.sparse:
+            return float(_sparse_loss(self.T, self.fs, 2.0, 'zero', part=self.part, out=self.out).item())
+        return self.half_v2 - float(self._vy().item()) + 0.5 * float(self._yy().item())
+
+
 class NTF(nn.Module):
     """Non-negative CP factorisation ``V (I, J, K) ~ sum_r A[:, r] x B[:, r] x C[:, r]``.
 
@@ -415,7 +564,8 @@ class NTF(nn.Module):
         return torch.einsum('ir,jr,kr->ijk', A, B, Cf)
 
     def fit(self, V: Tensor, beta: float = 1, tol: float = 1e-4, max_iter: int = 200, verbose: bool = False, alpha: float = 0,
-            l1_ratio: float = 0, weights=None, unstored: Optional[str] = None, tile: Optional[str] = None) -> int:
+            l1_ratio: float = 0, weights=None, unstored: Optional[str] = None, tile: Optional[str] = None,
+            solver: str = 'mu') -> int:
         """Fit the trainable factors to ``V`` by multiplicative updates: one iteration updates modes 0, 1, 2 in that order.
         Loss checkpoints and the stop rule are ``NMF.fit``'s (after iterations 9, 19, ...: stop when
         ``(previous - loss) / loss_init < tol``); returns the number of iterations.  ``weights``: None, or a dense tensor of
@@ -426,12 +576,32 @@ class NTF(nn.Module):
 
         A 3-D sparse COO ``V`` (or a ``SparseNtfTarget``) is fitted over its stored entries when ``unstored`` says how to
         read the others: ``'missing'`` -- unknown (ratings, unsampled triples; every beta, beta <= 0 needs positive stored
-        values), ``'zero'`` -- observed zeros (count tensors; beta in {1, 2}).  Nothing of the dense tensor's size exists."""
+        values), ``'zero'`` -- observed zeros (count tensors; beta in {1, 2}).  Nothing of the dense tensor's size exists.
+
+        ``solver``: 'mu' (the multiplicative update) or 'hals' -- cyclic coordinate descent on the Frobenius objective
+        (Cichocki & Phan 2009), beta = 2 only, dense unweighted targets and sparse ones with ``unstored='zero'``: a half-step is
+        one MTTKRP of ``V`` (``ntf_mttkrp``, ``V`` read once, no reconstruction), two Gram matrices and one sweep over the
+        rank (``hals.hals_sweep``); it reaches in a few iterations the loss MU needs hundreds for.  Before the first half-step
+        the trainable factors are scaled once by the scalar that fits ``V`` best and clamped to >= eps; an MU fit can
+        continue from the result.  The dense loss of a checkpoint comes from the last numerator and the Gram matrices
+        (no pass over ``V``); it is a difference of numbers of the size of ``|V|^2`` and loses digits when the fit is
+        nearly exact.  ``tile`` chooses the MTTKRP's wave arrangement as it chooses MU's tile."""
+        if solver not in ('mu', 'hals'):
+            raise ValueError(f"solver must be 'mu' or 'hals', got {solver!r}")
+        if solver == 'hals':
+            if float(beta) != 2.0:
+                raise NotImplementedError(f"solver='hals' minimises the Frobenius objective: beta = 2, got {float(beta):g}")
+            if weights is not None:
+                raise NotImplementedError("solver='hals' takes no weights: every owner row would need its own Gram matrix; "
+                                          "use solver='mu'")
+            if unstored == 'missing':
+                raise NotImplementedError("solver='hals' cannot read unstored entries as missing: every owner row would "
+                                          "need its own Gram matrix; use solver='mu'")
         _check_tile(tile)
         if unstored is not None:
             if tile is not None:
                 raise NotImplementedError('tile= chooses between the dense kernels; a sparse target has one kernel')
-            return self._fit_sparse(V, float(beta), tol, max_iter, verbose, alpha, l1_ratio, weights, unstored)
+            return self._fit_sparse(V, float(beta), tol, max_iter, verbose, alpha, l1_ratio, weights, unstored, solver)
         if not isinstance(V, Tensor):
             raise ValueError(f'NTF.fit takes a dense 3-D tensor, got {type(V).__name__}')
         if V.is_sparse:
@@ -457,7 +627,7 @@ class NTF(nn.Module):
             for f in self.factors:
                 f.data = f.data.float().contiguous()
             try:
-                return self.fit(V, beta, tol, max_iter, verbose, alpha, l1_ratio, weights, tile=tile)
+                return self.fit(V, beta, tol, max_iter, verbose, alpha, l1_ratio, weights, tile=tile, solver=solver)
             finally:
                 for f, k in zip(self.factors, keep):
                     f32, f.data = f.data, k
@@ -473,15 +643,22 @@ class NTF(nn.Module):
             if not f.data.is_contiguous():
                 f.data = f.data.contiguous()
         fs = [f.data for f in self.factors]
-        lib, (I, J, K) = _capi.load(), T.shape
-        r_pad = lib.nmfmu_pad_rank(self.rank)
-        ws = torch.empty(max(_tile_entries(lib, tile, d, I * J * K // d, r_pad)[0](d, I * J * K // d, r_pad, 0) for d in T.shape),
-                         dtype=torch.float32, device=T.device)      # per mode by the tile that mode takes
-        part = torch.empty(lib.nmfmu_ntf_loss_parts(I, J, K), dtype=torch.float64, device=T.device)
-        out = torch.zeros(1, dtype=torch.float64, device=T.device)
+        if solver == 'hals':
+            eng = _HalsNtf(T, fs, [f.requires_grad for f in self.factors], step[0], step[1], tile)
+            divergence, half_step = eng.divergence, eng.half_step
+        else:
+            lib, (I, J, K) = _capi.load(), T.shape
+            r_pad = lib.nmfmu_pad_rank(self.rank)
+            ws = torch.empty(max(_tile_entries(lib, tile, d, I * J * K // d, r_pad)[0](d, I * J * K // d, r_pad, 0)
+                                 for d in T.shape), dtype=torch.float32, device=T.device)      # per mode by the tile that mode takes
+            part = torch.empty(lib.nmfmu_ntf_loss_parts(I, J, K), dtype=torch.float64, device=T.device)
+            out = torch.zeros(1, dtype=torch.float64, device=T.device)
 
-        def divergence() -> float:
-            return float(_ntf_loss(T, fs, beta, part, out).item())
+            def divergence() -> float:
+                return float(_ntf_loss(T, fs, beta, part, out).item())
+
+            def half_step(mode: int) -> None:
+                _ntf_call(T, fs, mode, beta, step=step, _ws=ws, tile=tile)
 
         loss_init = previous = _sqrt2(divergence())      # nmf.py:355-363
         pbar = None
@@ -493,7 +670,7 @@ class NTF(nn.Module):
             for n_iter in range(max_iter):
                 for mode, f in enumerate(self.factors):
                     if f.requires_grad:
-                        _ntf_call(T, fs, mode, beta, step=step, _ws=ws, tile=tile)
+                        half_step(mode)
                 if n_iter % 10 == 9:
                     loss = _sqrt2(divergence())
                     if pbar is not None:
@@ -507,7 +684,7 @@ class NTF(nn.Module):
                 pbar.close()
         return n_iter + 1
 
-    def _fit_sparse(self, V, beta, tol, max_iter, verbose, alpha, l1_ratio, weights, unstored) -> int:
+    def _fit_sparse(self, V, beta, tol, max_iter, verbose, alpha, l1_ratio, weights, unstored, solver='mu') -> int:
         """``fit`` on a sparse target: the refusals in their order, then ``fit``'s loop on ``nmfmu_sp_ntf_step``."""
         if unstored not in ('zero', 'missing'):
             raise ValueError(f"unstored must be 'zero' or 'missing', got {unstored!r}")
@@ -525,7 +702,7 @@ class NTF(nn.Module):
             for f in self.factors:
                 f.data = f.data.float().contiguous()
             try:
-                return self._fit_sparse(V, beta, tol, max_iter, verbose, alpha, l1_ratio, weights, unstored)
+                return self._fit_sparse(V, beta, tol, max_iter, verbose, alpha, l1_ratio, weights, unstored, solver)
             finally:
                 for f, k in zip(self.factors, keep):
                     f32, f.data = f.data, k
@@ -540,15 +717,22 @@ class NTF(nn.Module):
             if not f.data.is_contiguous():
                 f.data = f.data.contiguous()
         fs = [f.data for f in self.factors]
-        lib = _capi.load()
-        r_pad = lib.nmfmu_pad_rank(self.rank)
-        ws = torch.empty(max(1, *(lib.nmfmu_sp_ntf_ws(m['n_ws'], r_pad) for m in T.modes)), dtype=torch.float32,
-                         device=T.device)
-        part = torch.empty((T.modes[0]['seg'].shape[0] + 3) // 4, dtype=torch.float64, device=T.device)
-        out = torch.zeros(1, dtype=torch.float64, device=T.device)
+        if solver == 'hals':
+            eng = _HalsNtf(T, fs, [f.requires_grad for f in self.factors], step[0], step[1])
+            divergence, half_step = eng.divergence, eng.half_step
+        else:
+            lib = _capi.load()
+            r_pad = lib.nmfmu_pad_rank(self.rank)
+            ws = torch.empty(max(1, *(lib.nmfmu_sp_ntf_ws(m['n_ws'], r_pad) for m in T.modes)), dtype=torch.float32,
+                             device=T.device)
+            part = torch.empty((T.modes[0]['seg'].shape[0] + 3) // 4, dtype=torch.float64, device=T.device)
+            out = torch.zeros(1, dtype=torch.float64, device=T.device)
 
-        def divergence() -> float:
-            return float(_sparse_loss(T, fs, beta, unstored, part=part, out=out).item())
+            def divergence() -> float:
+                return float(_sparse_loss(T, fs, beta, unstored, part=part, out=out).item())
+
+            def half_step(mode: int) -> None:
+                _sparse_call(T, fs, mode, beta, unstored, step=step, _ws=ws)
 
         loss_init = previous = _sqrt2(divergence())      # nmf.py:355-363
         pbar = None
@@ -560,7 +744,7 @@ class NTF(nn.Module):
             for n_iter in range(max_iter):
                 for mode, f in enumerate(self.factors):
                     if f.requires_grad:
-                        _sparse_call(T, fs, mode, beta, unstored, step=step, _ws=ws)
+                        half_step(mode)
                 if n_iter % 10 == 9:
                     loss = _sqrt2(divergence())
                     if pbar is not None:
