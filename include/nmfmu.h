@@ -104,6 +104,8 @@ extern "C" {
                                   unstored = 'missing' | 'zero'; added at ABI 10, additive);
                                   nmfmu_ntf_mttkrp / nmfmu_ntf_mttkrp_ws (the dense MTTKRP of a mode, the numerator of
                                   ntf.NTF.fit(solver='hals'); added at ABI 10, additive);
+                                  nmfmu_ntf_mttkrp_x3 (that MTTKRP in split bf16, ntf.NTF.fit(solver='hals', precision='bf16x3');
+                                  added at ABI 10, additive);
                                10: nmfmu_plca_normalize / nmfmu_plca_z / nmfmu_plca3 take alpha as double (an argument changed its
                                   type: not additive).  The Dirichlet prior adds fp32(alpha - 1) with the subtraction in double,
                                   as the reference's in-place add does; fp32(alpha) - 1.f was off by 4.7e-5 relative at
@@ -1040,6 +1042,13 @@ int nmfmu_ntf_tile(int rows, int contraction, int r_pad);
 int64_t nmfmu_ntf_mttkrp_ws(int rows, int contraction, int r_pad, int nsplit, int tile);
 int nmfmu_ntf_mttkrp(const float* V, int I, int J, int K, int mode, const float* pa, const float* pb, int rank, int r_pad,
                      int nsplit, int tile, float* ws, float* num, void* stream);
+/* The same MTTKRP in split bf16 (csrc/nmfmu_ntf_mttkrp_x3.hip, precision='bf16x3'): V and the Khatri-Rao rows fl32(pa pb) are
+ * each held as two bf16 planes (hi = bf16(x), lo = bf16(x - hi), RNE) and a product is three v_mfma_f32_32x32x16_bf16 into fp32
+ * (lo hi, hi lo, hi hi; lo lo is dropped): every element within 3 2^-18 (1 + 2^-8) + (3 L + 64) 2^-24 relative of the exact sum
+ * for non-negative inputs, L the contraction length.  V is still read once, as fp32, never through LDS.  Arguments, workspace
+ * (nmfmu_ntf_mttkrp_ws), parts, checks, their order and the status codes are nmfmu_ntf_mttkrp's; bitwise repeatable. */
+int nmfmu_ntf_mttkrp_x3(const float* V, int I, int J, int K, int mode, const float* pa, const float* pb, int rank, int r_pad,
+                        int nsplit, int tile, float* ws, float* num, void* stream);
 
 /* ---- NTF on a sparse 3-way target: the fit over the STORED entries (additive entries) -----------------------------------------
  * Per mode the target is held sorted by (owner index, a, b), a < b the other two modes: seg / multi are the segment lists of

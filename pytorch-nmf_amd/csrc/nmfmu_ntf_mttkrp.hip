@@ -39,6 +39,7 @@
 #include "nmfmu_fused.h"
 #include "nmfmu_launch.h"
 #include "nmfmu_ntf_host.h"
+#include "nmfmu_ntf_mttkrp.h"
 #include "nmfmu_sparse_common.h"
 #include "nmfmu_wmu_tile.h"
 
@@ -55,22 +56,6 @@ struct MkCfg {
   static constexpr bool AHEAD = PR == kWmBK;                  // the run's rows travel one stage ahead in registers
   static constexpr int LDS_BYTES = STAGE * RP * 4;
 };
-
-struct MkArgs {
-  const float* V;
-  int64_t sO, sA;
-  int rows, nB, C;
-  const float *Pa, *Pb;
-  int rank, part_len;
-  float* out;      // + part * pstride: the part's plane [rows][RP]
-  int64_t pstride;
-};
-
-// the slice table of the 32-step run at wc: lane l & 31 holds a = (wc + l) / nB (0 past the part).  Called by every lane.
-__device__ __forceinline__ int mk_slices(int wc, int cend, int nB, int lane) {
-  const int c = wc + (lane & 31);
-  return c < cend ? c / nB : 0;
-}
 
 // bv / bw = Pa[a] / Pb[b] of the PR steps from wc + d0 over the full padded rank; zero in the padded columns and past the part.
 // lt: the thread's index among the LT threads that load this run.
@@ -245,20 +230,9 @@ __global__ void __launch_bounds__(256) mk_finish_kernel(const float* __restrict_
   }
 }
 
-// ---- the split: parts of whole stages ------------------------------------------------------------------------------------------
-inline int mk_stage(int tile) { return tile ? 4 * kWmBK : kWmBK; }
-inline int mk_stages(int contraction, int tile) { return (contraction + mk_stage(tile) - 1) / mk_stage(tile); }
-// nsplit == 0: the parts the fused tile of this arrangement would take; no empty part, only the last one may be short
-inline int mk_split(int rows, int contraction, int r_pad, int nsplit, int tile) {
-  const int want = nsplit > 0 ? nsplit
-                              : (tile ? nmfmu_ntf_short_nsplit(rows, contraction, r_pad) : nmfmu_ntf_nsplit(rows, contraction, r_pad));
-  const int stages = mk_stages(contraction, tile);
-  const int n = std::max(1, std::min(want, stages));
-  const int per = (stages + n - 1) / n;
-  return (stages + per - 1) / per;
-}
-inline int mk_part_len(int contraction, int parts, int tile) {
-  return (mk_stages(contraction, tile) + parts - 1) / parts * mk_stage(tile);
+void mk_finish_launch(const float* ws, int parts, int64_t plane, float* num, hipStream_t st) {
+  hipLaunchKernelGGL(mk_finish_kernel, dim3((unsigned)std::min<int64_t>((plane + 255) / 256, kWmFinishBlocks)), dim3(256), 0, st, ws,
+                     parts, plane, num);
 }
 
 }  // namespace nmfmu
@@ -274,17 +248,10 @@ int64_t nmfmu_ntf_mttkrp_ws(int rows, int contraction, int r_pad, int nsplit, in
 
 int nmfmu_ntf_mttkrp(const float* V, int I, int J, int K, int mode, const float* pa, const float* pb, int rank, int r_pad,
                      int nsplit, int tile, float* ws, float* num, void* stream) {
-  if (!ws || !num || nsplit < 0 || tile < 0 || tile > 1) return NMFMU_ERR_ARG;
-  if (const int rc = wmu_check(pb && I > 0 && J > 0 && K > 0 && mode >= 0 && mode <= 2, V, num, pa, rank, r_pad, true)) return rc;
-  const NtfMode md = ntf_mode(I, J, K, mode);
-  if ((int64_t)md.nA * md.nB > kNtfMaxContraction) return NMFMU_ERR_UNSUPPORTED;
-  const int rows = md.rows, contraction = md.nA * md.nB;
-  const int parts = mk_split(rows, contraction, r_pad, nsplit, tile);
-  if (parts > kNtfMaxParts) return NMFMU_ERR_UNSUPPORTED;      // a forced split
-  const int64_t plane = (int64_t)rows * r_pad;
-  const MkArgs a{V, md.sO, md.sA, rows, md.nB, contraction, pa, pb, rank, mk_part_len(contraction, parts, tile),
-                 parts == 1 ? num : ws, plane};
-  const dim3 grid((rows + (tile ? 32 : kWmRows) - 1) / (tile ? 32 : kWmRows), 1, parts);
+  MkPlan pl;
+  if (const int rc = mk_plan(V, I, J, K, mode, pa, pb, rank, r_pad, nsplit, tile, ws, num, &pl)) return rc;
+  const MkArgs& a = pl.a;
+  const dim3 grid = pl.grid;
   int rc = 0;
   for_rp(r_pad, [&](auto rp) {
     constexpr int RP = decltype(rp)::value;
@@ -292,15 +259,13 @@ int nmfmu_ntf_mttkrp(const float* V, int I, int J, int K, int mode, const float*
       constexpr bool O = decltype(outer)::value, S = decltype(shrt)::value;
       rc = launch_with_dynamic_lds<mk_kernel<RP, O, S>, 256, MkCfg<RP, S>::LDS_BYTES>(grid, nmfmu::S(stream), a);
     };
-    if (md.outer)
+    if (pl.outer)
       tile ? go(std::true_type{}, std::true_type{}) : go(std::true_type{}, std::false_type{});
     else
       tile ? go(std::false_type{}, std::true_type{}) : go(std::false_type{}, std::false_type{});
   });
   if (rc) return rc;
-  if (parts > 1)
-    hipLaunchKernelGGL(mk_finish_kernel, dim3((unsigned)std::min<int64_t>((plane + 255) / 256, kWmFinishBlocks)), dim3(256), 0,
-                       nmfmu::S(stream), ws, parts, plane, num);
+  if (pl.parts > 1) mk_finish_launch(ws, pl.parts, a.pstride, num, nmfmu::S(stream));
   return (int)hipGetLastError();
 }
 

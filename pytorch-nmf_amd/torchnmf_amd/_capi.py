@@ -205,6 +205,8 @@ SIGNATURES = {
     'nmfmu_ntf_mttkrp_ws': (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     'nmfmu_ntf_mttkrp': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                    C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'nmfmu_ntf_mttkrp_x3': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                      C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     'nmfmu_ntf_loss_parts': (C.c_int, [C.c_int, C.c_int, C.c_int]),
     'nmfmu_ntf_loss': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                  C.c_float, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),

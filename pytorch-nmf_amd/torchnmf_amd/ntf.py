@@ -14,7 +14,8 @@ of the factors).  ``sparse_ntf_terms`` / ``sparse_ntf_loss`` are the functional 
 ``fit(beta=2, solver='hals')`` is HALS (Cichocki & Phan 2009), the coordinate descent of ``NMF.fit(solver='hals')`` on tensors: a
 half-step is the MTTKRP ``num[o] = sum_(a,b) V(o, a, b) Pa[a] o Pb[b]`` (``ntf_mttkrp``: csrc/nmfmu_ntf_mttkrp.hip, ``V`` read once,
 no reconstruction; on a sparse 'zero' target the numerator of ``nmfmu_sp_ntf_terms``), two Gram matrices and one
-``nmfmu_hals_sweep``.
+``nmfmu_hals_sweep``.  ``precision='bf16x3'`` runs the dense MTTKRP in split bf16 (csrc/nmfmu_ntf_mttkrp_x3.hip: three bf16
+MFMAs per product); the default is exact fp32.
 """
 from __future__ import annotations
 
@@ -187,12 +188,18 @@ def ntf_loss(V, weights, factors: Sequence[Tensor], beta: float) -> Tensor:
     return _ntf_loss(T, fs, float(beta))[0]
 
 
+def _check_precision(precision) -> None:
+    if precision not in ('fp32', 'bf16x3'):
+        raise ValueError(f"precision must be 'fp32' or 'bf16x3', got {precision!r}")
+
+
 def _mttkrp_call(T: NtfTarget, factors: Sequence[Tensor], mode: int, nsplit: int = 0, tile=None, _fill=None, _ws=None,
-                 out=None) -> Tensor:
-    """``nmfmu_ntf_mttkrp`` of ``mode``: fp32 ``[dim_mode, r_pad]`` (``out`` or a new tensor).  ``factors``: three contiguous fp32
-    ``[dim_n, R]``.  Enqueued only.  ``tile``: None (``nmfmu_ntf_tile``'s choice for this mode), 'wide' or 'short'.  ``_fill``:
-    tests pre-fill the output and the workspace with it."""
+                 out=None, precision: str = 'fp32') -> Tensor:
+    """``nmfmu_ntf_mttkrp`` (``precision='bf16x3'``: ``nmfmu_ntf_mttkrp_x3``) of ``mode``: fp32 ``[dim_mode, r_pad]`` (``out`` or a
+    new tensor).  ``factors``: three contiguous fp32 ``[dim_n, R]``.  Enqueued only.  ``tile``: None (``nmfmu_ntf_tile``'s choice
+    for this mode), 'wide' or 'short'.  ``_fill``: tests pre-fill the output and the workspace with it."""
     _check_tile(tile)
+    _check_precision(precision)
     lib = _capi.load()
     I, J, K = T.shape
     pa, pb = (f for n, f in enumerate(factors) if n != mode)
@@ -208,8 +215,9 @@ def _mttkrp_call(T: NtfTarget, factors: Sequence[Tensor], mode: int, nsplit: int
     if _fill is not None:
         ws.fill_(_fill)
         num.fill_(_fill)
-    _capi.check(lib.nmfmu_ntf_mttkrp(T.V.data_ptr(), I, J, K, mode, pa.data_ptr(), pb.data_ptr(), R, r_pad, nsplit, short,
-                                     ws.data_ptr(), num.data_ptr(), _stream()), 'nmfmu_ntf_mttkrp')
+    name = 'nmfmu_ntf_mttkrp' if precision == 'fp32' else 'nmfmu_ntf_mttkrp_x3'
+    _capi.check(getattr(lib, name)(T.V.data_ptr(), I, J, K, mode, pa.data_ptr(), pb.data_ptr(), R, r_pad, nsplit, short,
+                                   ws.data_ptr(), num.data_ptr(), _stream()), name)
     return num
 
 
@@ -220,12 +228,16 @@ class _Dense:
         self.V, self.shape, self.device = V.detach().float().contiguous(), tuple(V.shape), V.device
 
 
-def ntf_mttkrp(V, factors: Sequence[Tensor], mode: int, nsplit: int = 0, tile=None) -> Tensor:
+def ntf_mttkrp(V, factors: Sequence[Tensor], mode: int, nsplit: int = 0, tile=None, precision: str = 'fp32') -> Tensor:
     """The MTTKRP of ``mode`` (0, 1 or 2): ``num[o, r] = sum_(a, b) V(o, a, b) Pa[a, r] Pb[b, r]`` over the other two modes, fp32
     ``[dim_mode, r_pad]`` with zeros in the padded rank columns -- the numerator of a Frobenius half-step, one pass over ``V``
     on the exact-fp32 MFMA kernel of csrc/nmfmu_ntf_mttkrp.hip.  ``V``: a dense ``[I, J, K]`` device tensor or an unweighted
-    ``NtfTarget``.  ``nsplit``: parts of the contraction (0: the library's rule).  ``tile``: as for ``ntf_terms``."""
+    ``NtfTarget``.  ``nsplit``: parts of the contraction (0: the library's rule).  ``tile``: as for ``ntf_terms``.
+    ``precision``: 'fp32', or 'bf16x3' -- the split-bf16 kernel of csrc/nmfmu_ntf_mttkrp_x3.hip: ``V`` and the Khatri-Rao rows
+    as bf16 hi and lo planes, three bf16 MFMAs per product, every element within ``3 2^-18 (1 + 2^-8) + (3 L + 64) 2^-24``
+    relative of the exact sum (``L``: the contraction length) at 16/3 of the fp32 MFMA rate."""
     _check_tile(tile)
+    _check_precision(precision)
     if isinstance(V, NtfTarget):
         if V.M is not None:
             raise ValueError('ntf_mttkrp takes an unweighted target')
@@ -235,7 +247,8 @@ def ntf_mttkrp(V, factors: Sequence[Tensor], mode: int, nsplit: int = 0, tile=No
     for t in (V.V if isinstance(V, NtfTarget) else V, *factors):
         _require_device(t, 'NTF')
     T = V if isinstance(V, NtfTarget) else _Dense(V)
-    return _mttkrp_call(T, [f.detach().float().contiguous() for f in factors], int(mode), nsplit=nsplit, tile=tile)
+    return _mttkrp_call(T, [f.detach().float().contiguous() for f in factors], int(mode), nsplit=nsplit, tile=tile,
+                        precision=precision)
 
 
 # ---- sparse targets: the stored entries only ------------------------------------------------------------------------------------
@@ -452,8 +465,9 @@ class _HalsNtf:
     checkpoint costs no pass over ``V``.  Like ``HalsEngine``'s, the value loses digits when the fit is nearly exact: it is a
     difference of numbers of the size of ``|V|^2``.  The sparse loss is ``_sparse_loss``."""
 
-    def __init__(self, T, fs, train, l1: float, l2: float, tile=None):
+    def __init__(self, T, fs, train, l1: float, l2: float, tile=None, precision: str = 'fp32'):
         self.T, self.fs, self.train, self.l1, self.l2, self.tile = T, fs, [bool(t) for t in train], l1, l2, tile
+        self.precision = precision      # of every dense numerator: the half-steps', the initial scale's and the loss's
         self.sparse = isinstance(T, SparseNtfTarget)
         self.lib = lib = _capi.load()
         self.rank = R = fs[0].shape[1]
@@ -482,7 +496,7 @@ class _HalsNtf:
     def _numerator(self, mode: int) -> Tensor:
         if self.sparse:
             return _sparse_call(self.T, self.fs, mode, 2.0, 'zero', _ws=self.ws)[0]
-        return _mttkrp_call(self.T, self.fs, mode, tile=self.tile, _ws=self.ws, out=self.bufs[mode])
+        return _mttkrp_call(self.T, self.fs, mode, tile=self.tile, _ws=self.ws, out=self.bufs[mode], precision=self.precision)
 
     def _vy(self) -> Tensor:
         """``<V, Y>`` of the current factors, a 0-dim float64 device tensor."""
@@ -565,7 +579,7 @@ class NTF(nn.Module):
 
     def fit(self, V: Tensor, beta: float = 1, tol: float = 1e-4, max_iter: int = 200, verbose: bool = False, alpha: float = 0,
             l1_ratio: float = 0, weights=None, unstored: Optional[str] = None, tile: Optional[str] = None,
-            solver: str = 'mu') -> int:
+            solver: str = 'mu', precision: str = 'fp32') -> int:
         """Fit the trainable factors to ``V`` by multiplicative updates: one iteration updates modes 0, 1, 2 in that order.
         Loss checkpoints and the stop rule are ``NMF.fit``'s (after iterations 9, 19, ...: stop when
         ``(previous - loss) / loss_init < tol``); returns the number of iterations.  ``weights``: None, or a dense tensor of
@@ -585,7 +599,13 @@ class NTF(nn.Module):
         the trainable factors are scaled once by the scalar that fits ``V`` best and clamped to >= eps; an MU fit can
         continue from the result.  The dense loss of a checkpoint comes from the last numerator and the Gram matrices
         (no pass over ``V``); it is a difference of numbers of the size of ``|V|^2`` and loses digits when the fit is
-        nearly exact.  ``tile`` chooses the MTTKRP's wave arrangement as it chooses MU's tile."""
+        nearly exact.  ``tile`` chooses the MTTKRP's wave arrangement as it chooses MU's tile.
+
+        ``precision``: 'fp32' (exact fp32, the default) or 'bf16x3' -- ``solver='hals'`` on a dense target only: every MTTKRP
+        of the fit (all modes, the initial scale's and the loss's) runs on the split-bf16 kernel (``ntf_mttkrp(...,
+        precision='bf16x3')``, about 1.2e-5 relative per element); the Gram matrices and the sweep stay fp32.  The checkpoint
+        loss inherits the numerator's error: it is already a difference of numbers of the size of ``|V|^2``, so its absolute
+        error grows to about 1.2e-5 ``<V, Y>``."""
         if solver not in ('mu', 'hals'):
             raise ValueError(f"solver must be 'mu' or 'hals', got {solver!r}")
         if solver == 'hals':
@@ -597,6 +617,13 @@ class NTF(nn.Module):
             if unstored == 'missing':
                 raise NotImplementedError("solver='hals' cannot read unstored entries as missing: every owner row would "
                                           "need its own Gram matrix; use solver='mu'")
+        _check_precision(precision)
+        if precision != 'fp32':
+            if solver != 'hals':
+                raise NotImplementedError("precision='bf16x3' is the MTTKRP of solver='hals'; solver='mu' is exact fp32 only")
+            if unstored is not None or isinstance(V, SparseNtfTarget) or (isinstance(V, Tensor) and V.is_sparse):
+                raise NotImplementedError("precision='bf16x3' is the dense MTTKRP of solver='hals'; sparse targets are exact "
+                                          "fp32 only")
         _check_tile(tile)
         if unstored is not None:
             if tile is not None:
@@ -627,7 +654,8 @@ class NTF(nn.Module):
             for f in self.factors:
                 f.data = f.data.float().contiguous()
             try:
-                return self.fit(V, beta, tol, max_iter, verbose, alpha, l1_ratio, weights, tile=tile, solver=solver)
+                return self.fit(V, beta, tol, max_iter, verbose, alpha, l1_ratio, weights, tile=tile, solver=solver,
+                                precision=precision)
             finally:
                 for f, k in zip(self.factors, keep):
                     f32, f.data = f.data, k
@@ -644,7 +672,7 @@ class NTF(nn.Module):
                 f.data = f.data.contiguous()
         fs = [f.data for f in self.factors]
         if solver == 'hals':
-            eng = _HalsNtf(T, fs, [f.requires_grad for f in self.factors], step[0], step[1], tile)
+            eng = _HalsNtf(T, fs, [f.requires_grad for f in self.factors], step[0], step[1], tile, precision)
             divergence, half_step = eng.divergence, eng.half_step
         else:
             lib, (I, J, K) = _capi.load(), T.shape

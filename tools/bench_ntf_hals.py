@@ -1,5 +1,5 @@
 """Time and iterations for solver='hals' to reach the loss solver='mu' has after 200 iterations, same |randn| start; the share of a
-HALS iteration spent in the Gram and sweep launches.  Dense 512^3 rank 64; sparse 65536 x 16384 x 24, 10 M stored, 'zero'."""
+HALS iteration spent in the Gram and sweep launches.  Dense 512^3 rank 64 in both precisions of the MTTKRP; sparse 65536 x 16384 x 24, 10 M stored, 'zero'."""
 import json
 import os
 import sys
@@ -31,7 +31,7 @@ def events(fn, reps=20):
     return a.elapsed_time(b) / reps
 
 
-def run(name, V, T, kw, loss, shape, R, out):
+def run(name, V, T, kw, loss, shape, R, out, precision='fp32'):
     g = torch.Generator().manual_seed(3)
     start = [torch.randn(d, R, generator=g).abs() for d in shape]
     lib = _capi.load()
@@ -41,10 +41,10 @@ def run(name, V, T, kw, loss, shape, R, out):
     _, mu_ms = timed(lambda: m.fit(V, beta=2, tol=-1e9, max_iter=200, **kw))
     mu_loss = loss([f.data for f in m.factors])
     h = ntf.NTF(factors=start).cuda()
-    h.fit(V, beta=2, tol=-1e9, max_iter=1, solver='hals', **kw)      # warm-up
+    h.fit(V, beta=2, tol=-1e9, max_iter=1, solver='hals', precision=precision, **kw)      # warm-up
     h = ntf.NTF(factors=start).cuda()
     fs = [f.data for f in h.factors]
-    eng = ntf._HalsNtf(T, fs, (True, True, True), 0.0, 0.0)
+    eng = ntf._HalsNtf(T, fs, (True, True, True), 0.0, 0.0, precision=precision)
     _, scale_ms = timed(eng._ensure_scaled)
     trace, iters, hals_ms = [loss(fs)], 0, scale_ms
     while trace[-1] > mu_loss and iters < 200:
@@ -61,7 +61,7 @@ def run(name, V, T, kw, loss, shape, R, out):
         num, G, own = eng._numerator(n), ntf._gram(lib, pa) * ntf._gram(lib, pb), fs[n].clone()
         parts['sweep'] += events(lambda: _sweep(own, num, num.stride(0), G, 0.0, 0.0))
     tot = sum(parts.values())
-    res = dict(case=name, shape=shape, rank=R, mu_200_ms=mu_ms, mu_200_loss=mu_loss, hals_iterations=iters, hals_ms=hals_ms,
+    res = dict(case=name, precision=precision, shape=shape, rank=R, mu_200_ms=mu_ms, mu_200_loss=mu_loss, hals_iterations=iters, hals_ms=hals_ms,
                hals_scale_ms=scale_ms, hals_loss=trace[-1], hals_trace=trace[:12], iteration_parts_ms=parts,
                gram_and_sweep_share=(parts['gram'] + parts['sweep']) / tot, hals_fit_loss_tracked=eng.divergence())
     print(json.dumps(res), flush=True)
@@ -75,7 +75,8 @@ def main():
     pf = [torch.rand(d, R, device='cuda', generator=g) for d in shape]
     V = torch.einsum('ir,jr,kr->ijk', *pf) * (0.9 + 0.2 * torch.rand(shape, device='cuda', generator=g))
     T = ntf.NtfTarget(V)
-    run('dense', V, T, {}, lambda fs: float(ntf._ntf_loss(T, fs, 2.0).item()), shape, R, out)
+    for precision in ('fp32', 'bf16x3'):      # the loss is nmfmu_ntf_loss in either: float64 sums over the reconstruction
+        run('dense', V, T, {}, lambda fs: float(ntf._ntf_loss(T, fs, 2.0).item()), shape, R, out, precision)
     del V, T
     shape, nnz = (65536, 16384, 24), 10_000_000
     idx = torch.stack([torch.randint(0, d, (nnz,), device='cuda', generator=g) for d in shape])

@@ -1,4 +1,5 @@
-"""nmfmu_ntf_mttkrp per mode against nmfmu_ntf_terms at beta = 2 (same shape, same tile), alternating, device events."""
+"""nmfmu_ntf_mttkrp per mode in both precisions (fp32, and bf16x3: nmfmu_ntf_mttkrp_x3) against nmfmu_ntf_terms at beta = 2 (same
+shape, same tile), the three routes alternating, device events."""
 import json
 import os
 import subprocess
@@ -10,7 +11,8 @@ import torch  # noqa: E402
 from torchnmf_amd import _capi, ntf  # noqa: E402
 
 HBM = 8.0e12      # bytes / s, the MI355X's nominal HBM3E bandwidth
-REPS, WINDOWS = 20, 7
+MFMA = {'fp32': 157.3e12, 'bf16x3': 2516.6e12 / 3}      # flop / s of the matrix pipes: 32x32x2f32, and 32x32x16 bf16 three times per product
+REPS, WINDOWS = 50, 7
 
 
 def smi():
@@ -52,20 +54,26 @@ def main():
                 ws_t = torch.empty(max(1, ntf._tile_entries(lib, tile, rows, c, r_pad)[0](rows, c, r_pad, 0)), device='cuda')
                 num = torch.empty(rows, r_pad, device='cuda')
                 new = lambda: ntf._mttkrp_call(T, fs, mode, tile=tile, _ws=ws_m, out=num)      # noqa: E731
+                x3 = lambda: ntf._mttkrp_call(T, fs, mode, tile=tile, _ws=ws_m, out=num, precision='bf16x3')      # noqa: E731
                 old = lambda: ntf._ntf_call(T, fs, mode, 2.0, _ws=ws_t, tile=tile)             # noqa: E731
                 ref = old()[0]
                 err = float(((new() - ref).abs() / ref.abs().clamp_min(1e-30)).max())
+                err3 = float(((x3() - ref).abs() / ref.abs().clamp_min(1e-30)).max())
                 for _ in range(3):
-                    new(), old()
+                    new(), x3(), old()
                 torch.cuda.synchronize()
-                tn, to = [], []
+                tn, t3, to = [], [], []
                 for _ in range(WINDOWS):
                     tn.append(window(new))
+                    t3.append(window(x3))
                     to.append(window(old))
-                tn.sort(), to.sort()
+                tn.sort(), t3.sort(), to.sort()
+                pad = -(-rows // (32 if tile == 'short' else 128)) * (32 if tile == 'short' else 128)
+                mfma_ms = {k: 2.0 * pad * c * r_pad / v * 1e3 for k, v in MFMA.items()}      # padded rows and rank are multiplied too
                 case = dict(shape=shape, rank=R, mode=mode, tile=tile, auto_tile=auto, mttkrp_ms=dict(median=tn[WINDOWS // 2], min=tn[0], max=tn[-1]),
+                            mttkrp_x3_ms=dict(median=t3[WINDOWS // 2], min=t3[0], max=t3[-1]),
                             fused_terms_ms=dict(median=to[WINDOWS // 2], min=to[0], max=to[-1]), hbm_floor_ms=floor_ms,
-                            max_rel_diff_vs_terms_num=err)
+                            mfma_floor_ms=mfma_ms, max_rel_diff_vs_terms_num=err, x3_max_rel_diff_vs_terms_num=err3)
                 out['cases'].append(case)
                 print(json.dumps(case), flush=True)
         del V, T
