@@ -102,6 +102,8 @@ extern "C" {
                                   nmfmu_sp_ntf_terms / nmfmu_sp_ntf_step / nmfmu_sp_ntf_loss / nmfmu_sp_ntf_ws /
                                   nmfmu_sp_ntf_lds_rows (ntf.NTF on sparse-COO tensors: the fit over the stored entries,
                                   unstored = 'missing' | 'zero'; added at ABI 10, additive);
+                                  nmfmu_sp_ntf_ccd_sweep (ntf.NTF.fit(solver='ccd'): coordinate descent over the stored entries
+                                  of a sparse 3-way tensor, unstored = 'missing', beta == 2; added at ABI 10, additive);
                                   nmfmu_ntf_mttkrp / nmfmu_ntf_mttkrp_ws (the dense MTTKRP of a mode, the numerator of
                                   ntf.NTF.fit(solver='hals'); added at ABI 10, additive);
                                   nmfmu_ntf_mttkrp_x3 (that MTTKRP in split bf16, ntf.NTF.fit(solver='hals', precision='bf16x3');
@@ -1343,6 +1345,28 @@ int nmfmu_sp_ccd_lds_rows(int rank);   /* entries per row whose panel rows fit t
 int nmfmu_sp_ccd_sweep(const int32_t* rowptr, const int32_t* idx, const float* vals, const int32_t* order, int n_rows,
                        float* owner, const float* panel, int n_panel, int rank, float l1, float l2, float* scratch,
                        float* panel_t, int limit, int lds_rows, int wg_rows, void* stream);
+
+/* ---- CCD on a sparse 3-way tensor: coordinate descent over the STORED entries, beta == 2 (additive entry; ntf.py, DESIGN.md
+ * section 40) -----------------------------------------------------------------------------------------------------------------
+ * nmfmu_sp_ntf_ccd_sweep: one pass over the rank on owner [n_rows][rank], in place, for one mode of a tensor whose unstored
+ * entries are MISSING.  rowptr / idx_a / idx_b / vals: the mode's copy of the entries sorted by owner row (ntf.SparseNtfTarget);
+ * idx_a / idx_b hold rows of pa [rows_a][rank] / pb [rows_b][rank], the factors of the other two modes.  With
+ *   q_e,k = fp32(pa[a_e][k] * pb[b_e][k])                                 (one rounded product, never fused into its use)
+ * every owner row runs nmfmu_sp_ccd_sweep's recurrence with q_e,k in the place of panel[j_e][k], in nmfmu_sp_ccd_sweep's
+ * arithmetic, order of operations and work split (order, wg_rows, limit, scratch [nnz floats]: as there; no LDS stage, no
+ * transposed panel): the result is bit for bit nmfmu_sp_ccd_sweep's on the [n_rows] x [nnz] matrix whose entry e names row e
+ * of the panel q.  A row without entries is not touched.
+ * vec: how a lane fetches the panel values -- 1: 4-byte loads, one coordinate at a time; 2: the rank in groups of four, one
+ * 16-byte load per panel, entry and group, where rank % 4 == 0 and pa, pb are 16-byte aligned (4-byte loads otherwise);
+ * 0: the library's rule (as 2).  No bit depends on it.  Plain vector stores, no atomics: a repeated call is bitwise identical.
+ * pa, pb, idx_a, idx_b, vals are only read.
+ * Null rowptr / idx_a / idx_b / vals / owner / pa / pb / scratch, owner == pa or pb, n_rows <= 0, rows_a / rows_b <= 0,
+ * rank <= 0, limit outside 0 .. 512, wg_rows < 0, vec outside 0 .. 2: NMFMU_ERR_ARG; rank > 256: NMFMU_ERR_UNSUPPORTED -- both
+ * before any device work. */
+int nmfmu_sp_ntf_ccd_sweep(const int32_t* rowptr, const int32_t* idx_a, const int32_t* idx_b, const float* vals,
+                           const int32_t* order, int n_rows, float* owner, const float* pa, int rows_a, const float* pb,
+                           int rows_b, int rank, float l1, float l2, float* scratch, int limit, int wg_rows, int vec,
+                           void* stream);
 
 /* ---- weighted CCD: unstored entries are zeros of confidence omega, beta == 2 (additive entry; wccd.py)
  * nmfmu_sp_wccd_sweep: one pass over the rank on owner [n_rows][rank], in place, for the objective

@@ -16,6 +16,12 @@ half-step is the MTTKRP ``num[o] = sum_(a,b) V(o, a, b) Pa[a] o Pb[b]`` (``ntf_m
 no reconstruction; on a sparse 'zero' target the numerator of ``nmfmu_sp_ntf_terms``), two Gram matrices and one
 ``nmfmu_hals_sweep``.  ``precision='bf16x3'`` runs the dense MTTKRP in split bf16 (csrc/nmfmu_ntf_mttkrp_x3.hip: three bf16
 MFMAs per product); the default is exact fp32.
+
+``fit(beta=2, solver='ccd', unstored='missing')`` is the coordinate descent of ``NMF.fit(solver='ccd')`` on the CP model (the
+CCD-TC of Karlsson, Kressner & Uschmajew 2016): with missing data every owner row has its own quadratic, so a half-step keeps
+the residuals of the row's stored entries and walks the rank once -- one ``nmfmu_sp_ntf_ccd_sweep`` call
+(csrc/nmfmu_sparse_ntf_ccd.hip: a wave per row, a workgroup per long row, two panel rows gathered per entry four coordinates
+at a time and multiplied in registers).  ``ntf_ccd_sweep`` is the functional form.
 """
 from __future__ import annotations
 
@@ -32,7 +38,8 @@ from .engine import mu_gamma
 from .nmf import _require_device, _sqrt2
 from .wmu import check_weights
 
-__all__ = ['NTF', 'NtfTarget', 'ntf_terms', 'ntf_loss', 'SparseNtfTarget', 'sparse_ntf_terms', 'sparse_ntf_loss', 'ntf_mttkrp']
+__all__ = ['NTF', 'NtfTarget', 'ntf_terms', 'ntf_loss', 'SparseNtfTarget', 'sparse_ntf_terms', 'sparse_ntf_loss', 'ntf_mttkrp',
+           'ntf_ccd_sweep']
 
 MAX_RANK = 256
 MAX_CONTRACTION = 1 << 30      # csrc/nmfmu_ntf.hip: the flat contraction steps of a mode are ints
@@ -544,6 +551,145 @@ class _HalsNtf:
         return self.half_v2 - float(self._vy().item()) + 0.5 * float(self._yy().item())
 
 
+def _ccd_order(m) -> Tensor:
+    """The hand-out list of a mode's rows, longest first (a stable device sort of the counts)."""
+    return torch.argsort(torch.diff(m['rowptr']), descending=True, stable=True).to(torch.int32)
+
+
+def _ccd_call(T: SparseNtfTarget, factors: Sequence[Tensor], mode: int, l1: float, l2: float, order: Tensor, scratch: Tensor,
+              limit: int = 0, wg_rows: int = 0, vec: int = 0) -> None:
+    """``nmfmu_sp_ntf_ccd_sweep`` on ``factors[mode]``, in place.  ``factors``: three contiguous fp32 ``[dim_n, R]``; ``order``:
+    int32 ``[dim_mode]``; ``scratch``: at least ``nnz`` floats.  Enqueued only."""
+    owner = factors[mode]
+    pa, pb = (f for n, f in enumerate(factors) if n != mode)
+    m = T.modes[mode]
+    assert tuple(f.shape for f in factors) == tuple((d, owner.shape[1]) for d in T.shape)
+    assert order.numel() == owner.shape[0] and scratch.numel() >= T.nnz
+    _capi.check(_capi.load().nmfmu_sp_ntf_ccd_sweep(
+        m['rowptr'].data_ptr(), SA.entries(m['idx_a'], T.spare), SA.entries(m['idx_b'], T.spare), SA.entries(m['vals'], T.spare),
+        order.data_ptr(), owner.shape[0], owner.data_ptr(), pa.data_ptr(), pa.shape[0], pb.data_ptr(), pb.shape[0],
+        owner.shape[1], l1, l2, scratch.data_ptr(), int(limit), int(wg_rows), int(vec), _stream()), 'nmfmu_sp_ntf_ccd_sweep')
+
+
+@torch.no_grad()
+def ntf_ccd_sweep(T, factors: Sequence[Tensor], mode: int, l1: float = 0.0, l2: float = 0.0, *, _limit: int = 0,
+                  _order: Tensor = None, _wg_rows: int = 0, _vec: int = 0) -> Tensor:
+    """One coordinate-descent pass over the rank on ``factors[mode]`` (contiguous fp32 ``[dim_mode, R]`` on the ROCm device), in
+    place, over the stored entries of ``T`` alone -- the half-step of ``NTF.fit(solver='ccd')``.  With
+    ``q_e,k = fp32(Pa[a_e, k] Pb[b_e, k])`` from the rows of the other two factors an entry names, every owner row with entries runs
+
+        r_e = v_e - sum_k F[i, k] q_e,k
+        for k = 0 .. R-1:   d = sum_e q_e,k^2      n = sum_e r_e q_e,k
+                            f' = max(eps, (n + F[i, k] d - l1) / (d + l2 + eps))
+                            r_e -= (f' - F[i, k]) q_e,k;   F[i, k] = f'
+
+    and a row without entries is not touched.  ``T``: a ``SparseNtfTarget`` or a 3-D sparse-COO device tensor.  The other two
+    factors are not written.  Returns ``factors[mode]``.  Raises ``NmfmuError`` for CPU tensors, ``NotImplementedError`` above
+    rank 256.  Bit for bit ``ccd.ccd_sweep`` on the ``dim_mode x nnz`` matrix whose entry e names row e of the panel ``q``.
+
+    ``_limit`` / ``_order`` / ``_wg_rows`` are ``ccd.ccd_sweep``'s, for the tests and the benchmark; ``_vec``: 0 -- the library's
+    rule, 1 -- 4-byte loads of the panel values, 2 -- the rank in groups of four with 16-byte loads where ``R % 4 == 0``.  A
+    row's bits depend on none of ``_limit``, ``_order`` and ``_vec``; ``_wg_rows`` moves rows between two summation orders."""
+    what = 'ntf_ccd_sweep'
+    if mode not in (0, 1, 2):
+        raise ValueError(f'{what}: mode must be 0, 1 or 2, got {mode!r}')
+    if not isinstance(T, SparseNtfTarget) and not (isinstance(T, Tensor) and T.is_sparse and T.dim() == 3):
+        raise ValueError(f'{what}: T must be a SparseNtfTarget or a 3-D sparse-COO tensor')
+    factors = list(factors)
+    if len(factors) != 3 or not all(isinstance(f, Tensor) for f in factors):
+        raise ValueError(f'{what}: factors must be three tensors [dim_n, R]')
+    names = ('factors[0]', 'factors[1]', 'factors[2]')
+    for t, name in (*zip(factors, names), (T, 'T')):
+        if t.device.type != 'cuda':
+            raise _capi.NmfmuError(f'{what}: {name} lives on {t.device}; torchnmf_amd computes on an MI355X only -- move '
+                                   f'the tensors with .cuda() (there is no CPU fallback)')
+    F = factors[mode]
+    for t, name in zip(factors, names):
+        if t.dtype != torch.float32:
+            raise TypeError(f'{what}: {name} must be float32, got {t.dtype}')
+        if t.device != F.device:
+            raise ValueError(f'{what}: {name} lives on {t.device}, factors[{mode}] on {F.device}')
+    if F.dim() != 2 or not F.is_contiguous():
+        raise ValueError(f'{what}: factors[{mode}] must be a contiguous 2-D tensor (it is updated in place)')
+    R = F.shape[1]
+    want = tuple((int(d), R) for d in T.shape)
+    if any(f.dim() != 2 for f in factors) or tuple(tuple(f.shape) for f in factors) != want:
+        raise ValueError(f'{what}: a {tuple(T.shape)} target needs factors {want}, got {[tuple(f.shape) for f in factors]}')
+    if not 0 <= int(_limit) <= 512:
+        raise ValueError(f'{what}: _limit must lie in 0 .. 512, got {_limit!r}')
+    if int(_wg_rows) < 0:
+        raise ValueError(f'{what}: _wg_rows must be >= 0, got {_wg_rows!r}')
+    if int(_vec) not in (0, 1, 2):
+        raise ValueError(f'{what}: _vec must be 0, 1 or 2, got {_vec!r}')
+    if R > MAX_RANK:
+        raise NotImplementedError(f'{what}: rank {R} > {MAX_RANK}, the limit of the sparse kernels')
+    if R == 0:
+        return F
+    if not isinstance(T, SparseNtfTarget):
+        T = SparseNtfTarget(T)
+    if T.nnz == 0:
+        return F
+    if _order is None:
+        order = _ccd_order(T.modes[mode])
+    else:
+        order = _order.to(device=F.device, dtype=torch.int32).contiguous()
+        if order.dim() != 1 or not torch.equal(torch.sort(order.long())[0], torch.arange(F.shape[0], device=F.device)):
+            raise ValueError(f'{what}: _order must be a permutation of the {F.shape[0]} rows of mode {mode}')
+    fs = [f.detach() if n == mode else f.detach().contiguous() for n, f in enumerate(factors)]
+    scratch = torch.empty(max(T.nnz, 4), dtype=torch.float32, device=F.device)
+    _ccd_call(T, fs, int(mode), float(l1), float(l2), order, scratch, int(_limit), int(_wg_rows), int(_vec))
+    return F
+
+
+class _CcdNtf:
+    """The half-steps and the loss of ``NTF.fit(beta=2, solver='ccd', unstored='missing')`` on the contiguous fp32 masters ``fs``,
+    updated in place.  A half-step of mode n is one ``nmfmu_sp_ntf_ccd_sweep`` call over that mode's sorted copy of the entries;
+    the loss is ``_sparse_loss`` over the stored entries.  Before the first half-step or loss the trainable factors are scaled
+    once, as ``CcdEngine`` does: ``a = sum_e v_e s_e / sum_e s_e^2`` over the stored entries -- ``<num, A> / <den, A>`` of mode 0's
+    beta = 2 'missing' terms, float64 dots -- each of the t trainable factors times ``a^(1/t)`` (skipped unless a is finite and
+    positive), then clamped to >= eps."""
+
+    def __init__(self, T: SparseNtfTarget, fs, train, l1: float, l2: float):
+        self.T, self.fs, self.train, self.l1, self.l2 = T, fs, [bool(t) for t in train], float(l1), float(l2)
+        self.rank = fs[0].shape[1]
+        self.orders = [_ccd_order(m) if on and T.nnz else None for m, on in zip(T.modes, self.train)]
+        self.scratch = torch.empty(max(T.nnz, 4), dtype=torch.float32, device=T.device)      # one for the three modes
+        self.part = torch.empty((T.modes[0]['seg'].shape[0] + 3) // 4, dtype=torch.float64, device=T.device)
+        self.out = torch.zeros(1, dtype=torch.float64, device=T.device)
+        self._scaled = False
+
+    def _ensure_scaled(self) -> None:
+        if self._scaled:
+            return
+        self._scaled = True
+        t = sum(self.train)
+        if t and self.T.nnz:
+            num, den = _sparse_call(self.T, self.fs, 0, 2.0, 'missing')
+            A = self.fs[0].double()
+            vs = float((num[:, :self.rank].double() * A).sum().item())
+            ss = float((den[:, :self.rank].double() * A).sum().item())
+            a = vs / ss if ss != 0 else float('nan')
+            if a > 0 and a != float('inf'):
+                for f, on in zip(self.fs, self.train):
+                    if on:
+                        f.mul_(a ** (1.0 / t))
+        for f, on in zip(self.fs, self.train):
+            if on:
+                f.clamp_(min=eps)
+
+    def half_step(self, mode: int) -> None:
+        if not self.train[mode]:
+            return
+        self._ensure_scaled()
+        if self.orders[mode] is not None:
+            _ccd_call(self.T, self.fs, mode, self.l1, self.l2, self.orders[mode], self.scratch)
+
+    def divergence(self) -> float:
+        """1/2 sum over the stored entries of (v - s)^2 (no regularisation terms).  One host sync."""
+        self._ensure_scaled()
+        return float(_sparse_loss(self.T, self.fs, 2.0, 'missing', part=self.part, out=self.out).item())
+
+
 class NTF(nn.Module):
     """Non-negative CP factorisation ``V (I, J, K) ~ sum_r A[:, r] x B[:, r] x C[:, r]``.
 
@@ -592,22 +738,36 @@ class NTF(nn.Module):
         read the others: ``'missing'`` -- unknown (ratings, unsampled triples; every beta, beta <= 0 needs positive stored
         values), ``'zero'`` -- observed zeros (count tensors; beta in {1, 2}).  Nothing of the dense tensor's size exists.
 
-        ``solver``: 'mu' (the multiplicative update) or 'hals' -- cyclic coordinate descent on the Frobenius objective
+        ``solver``: 'mu' (the multiplicative update), 'hals' or 'ccd'.  'hals' -- cyclic coordinate descent on the Frobenius objective
         (Cichocki & Phan 2009), beta = 2 only, dense unweighted targets and sparse ones with ``unstored='zero'``: a half-step is
         one MTTKRP of ``V`` (``ntf_mttkrp``, ``V`` read once, no reconstruction), two Gram matrices and one sweep over the
         rank (``hals.hals_sweep``); it reaches in a few iterations the loss MU needs hundreds for.  Before the first half-step
         the trainable factors are scaled once by the scalar that fits ``V`` best and clamped to >= eps; an MU fit can
         continue from the result.  The dense loss of a checkpoint comes from the last numerator and the Gram matrices
         (no pass over ``V``); it is a difference of numbers of the size of ``|V|^2`` and loses digits when the fit is
-        nearly exact.  ``tile`` chooses the MTTKRP's wave arrangement as it chooses MU's tile.
+        nearly exact.  ``tile`` chooses the MTTKRP's wave arrangement as it chooses MU's tile.  'ccd' -- the same coordinate
+        descent for a sparse target with ``unstored='missing'`` (beta = 2, no weights), where every owner row has its own
+        quadratic: a half-step is one sweep over the stored entries with a maintained residual (``ntf_ccd_sweep``), at the
+        order of one multiplicative half-step; the same once-only scale and clamp, over the stored entries.  A dense target
+        or ``unstored='zero'`` has ``solver='hals'``.
 
         ``precision``: 'fp32' (exact fp32, the default) or 'bf16x3' -- ``solver='hals'`` on a dense target only: every MTTKRP
         of the fit (all modes, the initial scale's and the loss's) runs on the split-bf16 kernel (``ntf_mttkrp(...,
         precision='bf16x3')``, about 1.2e-5 relative per element); the Gram matrices and the sweep stay fp32.  The checkpoint
         loss inherits the numerator's error: it is already a difference of numbers of the size of ``|V|^2``, so its absolute
         error grows to about 1.2e-5 ``<V, Y>``."""
-        if solver not in ('mu', 'hals'):
-            raise ValueError(f"solver must be 'mu' or 'hals', got {solver!r}")
+        if solver not in ('mu', 'hals', 'ccd'):
+            raise ValueError(f"solver must be 'mu' or 'hals', or 'ccd' on a sparse target with unstored='missing'; got {solver!r}")
+        if solver == 'ccd':
+            if float(beta) != 2.0:
+                raise NotImplementedError(f"solver='ccd' minimises the Frobenius objective over the stored entries: beta = 2, "
+                                          f"got {float(beta):g}")
+            if weights is not None:
+                raise NotImplementedError("solver='ccd' takes no weights: the stored set of a sparse target is the mask; "
+                                          "use solver='mu'")
+            if unstored != 'missing':
+                raise NotImplementedError("solver='ccd' fits the stored entries of a sparse target read with "
+                                          "unstored='missing'; for a dense target or unstored='zero' use solver='hals'")
         if solver == 'hals':
             if float(beta) != 2.0:
                 raise NotImplementedError(f"solver='hals' minimises the Frobenius objective: beta = 2, got {float(beta):g}")
@@ -616,7 +776,7 @@ class NTF(nn.Module):
                                           "use solver='mu'")
             if unstored == 'missing':
                 raise NotImplementedError("solver='hals' cannot read unstored entries as missing: every owner row would "
-                                          "need its own Gram matrix; use solver='mu'")
+                                          "need its own Gram matrix; use solver='mu' or solver='ccd'")
         _check_precision(precision)
         if precision != 'fp32':
             if solver != 'hals':
@@ -747,6 +907,9 @@ class NTF(nn.Module):
         fs = [f.data for f in self.factors]
         if solver == 'hals':
             eng = _HalsNtf(T, fs, [f.requires_grad for f in self.factors], step[0], step[1])
+            divergence, half_step = eng.divergence, eng.half_step
+        elif solver == 'ccd':
+            eng = _CcdNtf(T, fs, [f.requires_grad for f in self.factors], step[0], step[1])
             divergence, half_step = eng.divergence, eng.half_step
         else:
             lib = _capi.load()
