@@ -104,6 +104,9 @@ extern "C" {
                                   unstored = 'missing' | 'zero'; added at ABI 10, additive);
                                   nmfmu_sp_ntf_ccd_sweep (ntf.NTF.fit(solver='ccd'): coordinate descent over the stored entries
                                   of a sparse 3-way tensor, unstored = 'missing', beta == 2; added at ABI 10, additive);
+                                  nmfmu_sp_ntf_ccd_gram / nmfmu_sp_ntf_ccd_gram_ws / nmfmu_sp_ntf_ccd_gram_part (that half-step
+                                  for rows with many stored entries: the row's normal equations on an fp32 MFMA kernel,
+                                  ntf.ntf_ccd_sweep(gram_rows=); added at ABI 10, additive);
                                   nmfmu_ntf_mttkrp / nmfmu_ntf_mttkrp_ws (the dense MTTKRP of a mode, the numerator of
                                   ntf.NTF.fit(solver='hals'); added at ABI 10, additive);
                                   nmfmu_ntf_mttkrp_x3 (that MTTKRP in split bf16, ntf.NTF.fit(solver='hals', precision='bf16x3');
@@ -1367,6 +1370,38 @@ int nmfmu_sp_ntf_ccd_sweep(const int32_t* rowptr, const int32_t* idx_a, const in
                            const int32_t* order, int n_rows, float* owner, const float* pa, int rows_a, const float* pb,
                            int rows_b, int rank, float l1, float l2, float* scratch, int limit, int wg_rows, int vec,
                            void* stream);
+
+/* ---- the same half-step through a row's normal equations, for rows with many stored entries (additive entries; ntf.py,
+ * DESIGN.md section 41) ---------------------------------------------------------------------------------------------------------
+ * nmfmu_sp_ntf_ccd_gram: for every row i = rows[0 .. n_long) of owner [.][rank], in place, with q_e,k as above:
+ *   Q = sum_e q_e q_e^T,  b = sum_e v_e q_e   over the row's stored entries, exact-fp32 MFMA, only the 32 x 32 blocks on and
+ *   above the diagonal; then for k = 0 .. rank-1
+ *   f_k = max(eps, ((b_k - l1) - sum_{j != k} f_j Q[min(j,k)][max(j,k)]) / ((Q[k][k] + l2) + eps)),   eps = 2^-23
+ * -- the coordinate minimiser nmfmu_sp_ntf_ccd_sweep computes from its residuals, in other arithmetic: OTHER BITS than the
+ * sweep's.  A row is cut into parts of `part` entries (a positive multiple of 32; the last part of a row is shorter), one
+ * workgroup each; row rows[r] owns the parts row_part[r] .. row_part[r + 1] - 1 (row_part [n_long + 1], row_part[0] == 0,
+ * row_part[n_long] == n_parts, every row at least one part: ceil(count / part) of them) and part_row [n_parts] names r for
+ * every part.  A part's sums go to its slot of ws with plain stores and a row's parts are added in part order: no atomics, a
+ * repeated call is bitwise identical, a row's bits depend on its entries, the panels and `part` alone.  ws holds
+ * nmfmu_sp_ntf_ccd_gram_ws(n_parts, n_long, rank) floats.  rowptr / idx_a / idx_b / vals / pa / pb / vec: as for
+ * nmfmu_sp_ntf_ccd_sweep; every row of `rows` must have entries; the other rows of owner are not touched.
+ * Null pointers, owner == pa or pb, n_long <= 0, n_parts < n_long, rows_a / rows_b <= 0, rank <= 0, part <= 0 or not a multiple
+ * of 32, vec outside 0 .. 2: NMFMU_ERR_ARG; rank > 256: NMFMU_ERR_UNSUPPORTED -- both before any device work.
+ * nmfmu_sp_ntf_ccd_gram_ws (host only): n_parts * (B * 1024 + r_pad) + n_long * r_pad^2 floats, r_pad = 32 / 64 / 128 / 256 the
+ * padded rank, B = (r_pad / 32)(r_pad / 32 + 1) / 2; 0 for arguments the entry above refuses.
+ * nmfmu_sp_ntf_ccd_gram_part (host only): the library's part length for n_long rows holding `entries` stored entries together,
+ * `longest` in the longest, on a device of `cus` compute units (<= 0: 256) -- a pure function of its arguments.  With
+ * most = 2^26 / (B * 1024 + r_pad + r_pad^2), the parts a 256 MiB workspace admits, and want = min(4 cus, most):
+ *   part = ceil(entries / (want > 2 n_long ? want - n_long : want / 2)), at least ceil(longest / (most - 1)) and at least 256,
+ * rounded up to a multiple of 32: about `want` parts where the rows are few, and any one row stays under the cap.  A caller
+ * with more rows than that launches them in batches of at most `most` parts (ntf.py does).  0 for entries / n_long / longest
+ * <= 0, longest > entries, rank outside 1 .. 256. */
+int nmfmu_sp_ntf_ccd_gram(const int32_t* rowptr, const int32_t* idx_a, const int32_t* idx_b, const float* vals,
+                          const int32_t* rows, const int32_t* row_part, const int32_t* part_row, int n_long, int n_parts,
+                          int part, float* owner, const float* pa, int rows_a, const float* pb, int rows_b, int rank, float l1,
+                          float l2, float* ws, int vec, void* stream);
+int64_t nmfmu_sp_ntf_ccd_gram_ws(int n_parts, int n_long, int rank);
+int nmfmu_sp_ntf_ccd_gram_part(int64_t entries, int n_long, int longest, int rank, int cus);
 
 /* ---- weighted CCD: unstored entries are zeros of confidence omega, beta == 2 (additive entry; wccd.py)
  * nmfmu_sp_wccd_sweep: one pass over the rank on owner [n_rows][rank], in place, for the objective

@@ -225,6 +225,11 @@ SIGNATURES = {
     'nmfmu_sp_ntf_ccd_sweep': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                          C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p,
                                          C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    'nmfmu_sp_ntf_ccd_gram': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                        C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_void_p]),
+    'nmfmu_sp_ntf_ccd_gram_ws': (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    'nmfmu_sp_ntf_ccd_gram_part': (C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]),
     'nmfmu_bmu_nsplit': (C.c_int, [C.c_int, C.c_int, C.c_int]),
     'nmfmu_bmu_ws': (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     'nmfmu_bmu_terms': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,

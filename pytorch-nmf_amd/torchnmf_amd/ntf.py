@@ -21,7 +21,9 @@ MFMAs per product); the default is exact fp32.
 CCD-TC of Karlsson, Kressner & Uschmajew 2016): with missing data every owner row has its own quadratic, so a half-step keeps
 the residuals of the row's stored entries and walks the rank once -- one ``nmfmu_sp_ntf_ccd_sweep`` call
 (csrc/nmfmu_sparse_ntf_ccd.hip: a wave per row, a workgroup per long row, two panel rows gathered per entry four coordinates
-at a time and multiplied in registers).  ``ntf_ccd_sweep`` is the functional form.
+at a time and multiplied in registers).  ``ntf_ccd_sweep`` is the functional form.  ``gram_rows=`` sends the rows above that
+many entries through their own normal equations instead (csrc/nmfmu_sparse_ntf_ccd_gram.hip: a row cut into parts over the
+whole device, ``Q = sum q q^T`` by exact-fp32 MFMA, then the coordinate sweep on ``Q``) -- the route for a mode of few, long rows.
 """
 from __future__ import annotations
 
@@ -559,21 +561,86 @@ def _ccd_order(m) -> Tensor:
 def _ccd_call(T: SparseNtfTarget, factors: Sequence[Tensor], mode: int, l1: float, l2: float, order: Tensor, scratch: Tensor,
               limit: int = 0, wg_rows: int = 0, vec: int = 0) -> None:
     """``nmfmu_sp_ntf_ccd_sweep`` on ``factors[mode]``, in place.  ``factors``: three contiguous fp32 ``[dim_n, R]``; ``order``:
-    int32 ``[dim_mode]``; ``scratch``: at least ``nnz`` floats.  Enqueued only."""
+    int32, the rows to sweep (all ``dim_mode`` of them, or the rows the normal-equations route leaves); ``scratch``: at least
+    ``nnz`` floats.  Enqueued only."""
     owner = factors[mode]
     pa, pb = (f for n, f in enumerate(factors) if n != mode)
     m = T.modes[mode]
     assert tuple(f.shape for f in factors) == tuple((d, owner.shape[1]) for d in T.shape)
-    assert order.numel() == owner.shape[0] and scratch.numel() >= T.nnz
+    assert 0 < order.numel() <= owner.shape[0] and scratch.numel() >= T.nnz
     _capi.check(_capi.load().nmfmu_sp_ntf_ccd_sweep(
         m['rowptr'].data_ptr(), SA.entries(m['idx_a'], T.spare), SA.entries(m['idx_b'], T.spare), SA.entries(m['vals'], T.spare),
-        order.data_ptr(), owner.shape[0], owner.data_ptr(), pa.data_ptr(), pa.shape[0], pb.data_ptr(), pb.shape[0],
+        order.data_ptr(), order.numel(), owner.data_ptr(), pa.data_ptr(), pa.shape[0], pb.data_ptr(), pb.shape[0],
         owner.shape[1], l1, l2, scratch.data_ptr(), int(limit), int(wg_rows), int(vec), _stream()), 'nmfmu_sp_ntf_ccd_sweep')
+
+
+GRAM_CAP = 1 << 26      # floats: the workspace cap of nmfmu_sp_ntf_ccd_gram_part (256 MiB)
+
+
+def _check_gram_rows(gram_rows, what: str) -> None:
+    if gram_rows is not None and (isinstance(gram_rows, bool) or not isinstance(gram_rows, int) or gram_rows < 0):
+        raise ValueError(f'{what}: gram_rows must be None or an integer >= 0, got {gram_rows!r}')
+
+
+def _gram_plan(T: SparseNtfTarget, mode: int, gram_rows: int, part: int, rank: int) -> dict:
+    """The parts plan of the normal-equations route for one mode, built once per (target, mode, gram_rows, part, rank) and kept
+    on the target: the rows with more than ``gram_rows`` stored entries, longest first, in batches whose workspace stays under
+    ``GRAM_CAP`` -- per batch ``(rows, row_part, part_row, n_long, n_parts)`` as ``nmfmu_sp_ntf_ccd_gram`` takes them -- the part
+    length (``part`` == 0: the library's rule), the workspace floats of the largest batch, and ``rest``: the other rows in the
+    sweep's order.  Building it reads the row counts back once; a half-step with a plan enqueues only."""
+    plans = T.__dict__.setdefault('_gram_plans', {})
+    key = (mode, gram_rows, part, rank)
+    if key in plans:
+        return plans[key]
+    lib, m = _capi.load(), T.modes[mode]
+    counts, order = torch.diff(m['rowptr']), _ccd_order(m)
+    n_long = int((counts > gram_rows).sum().item())
+    plan = dict(rest=order[n_long:].contiguous(), batches=[], ws=0, part=part)
+    if n_long:
+        rows = order[:n_long].contiguous()
+        c = counts[rows.long()].cpu().long()      # descending
+        if part == 0:
+            part = lib.nmfmu_sp_ntf_ccd_gram_part(int(c.sum()), n_long, int(c[0]), rank,
+                                                  torch.cuda.get_device_properties(T.device).multi_processor_count)
+        most = GRAM_CAP // lib.nmfmu_sp_ntf_ccd_gram_ws(1, 1, rank)      # parts of a batch, each counted with a row's image
+        n_parts = (c + (part - 1)) // part
+        if int(n_parts[0]) > most:
+            raise ValueError(f'ntf_ccd_sweep: parts of {part} entries cut the longest row ({int(c[0])} entries) into '
+                             f'{int(n_parts[0])} parts, more than the {most} the workspace cap admits at rank {rank}')
+        ends = torch.cat([torch.zeros(1, dtype=n_parts.dtype), torch.cumsum(n_parts, 0)])      # row r: parts ends[r] .. ends[r+1]-1
+        at = 0
+        while at < n_long:
+            end = int(torch.searchsorted(ends, int(ends[at]) + most, right=True)) - 1      # rows at .. end-1 hold <= most parts
+            row_part = (ends[at:end + 1] - ends[at]).to(torch.int32)
+            part_row = torch.repeat_interleave(torch.arange(end - at, dtype=torch.int32), n_parts[at:end])
+            k = int(row_part[-1])
+            plan['batches'].append((rows[at:end].contiguous(), row_part.to(T.device), part_row.to(T.device), end - at, k))
+            plan['ws'] = max(plan['ws'], lib.nmfmu_sp_ntf_ccd_gram_ws(k, end - at, rank))
+            at = end
+        plan['part'] = part
+    plans[key] = plan
+    return plan
+
+
+def _gram_call(T: SparseNtfTarget, factors: Sequence[Tensor], mode: int, l1: float, l2: float, plan: dict, ws: Tensor,
+               vec: int = 0) -> None:
+    """``nmfmu_sp_ntf_ccd_gram`` on the long rows of ``plan``, batch after batch through one workspace.  Enqueued only."""
+    owner = factors[mode]
+    pa, pb = (f for n, f in enumerate(factors) if n != mode)
+    m = T.modes[mode]
+    assert tuple(f.shape for f in factors) == tuple((d, owner.shape[1]) for d in T.shape) and ws.numel() >= plan['ws']
+    for rows, row_part, part_row, n_long, n_parts in plan['batches']:
+        _capi.check(_capi.load().nmfmu_sp_ntf_ccd_gram(
+            m['rowptr'].data_ptr(), m['idx_a'].data_ptr(), m['idx_b'].data_ptr(), m['vals'].data_ptr(), rows.data_ptr(),
+            row_part.data_ptr(), part_row.data_ptr(), n_long, n_parts, plan['part'], owner.data_ptr(), pa.data_ptr(),
+            pa.shape[0], pb.data_ptr(), pb.shape[0], owner.shape[1], l1, l2, ws.data_ptr(), int(vec), _stream()),
+            'nmfmu_sp_ntf_ccd_gram')
 
 
 @torch.no_grad()
 def ntf_ccd_sweep(T, factors: Sequence[Tensor], mode: int, l1: float = 0.0, l2: float = 0.0, *, _limit: int = 0,
-                  _order: Tensor = None, _wg_rows: int = 0, _vec: int = 0) -> Tensor:
+                  _order: Tensor = None, _wg_rows: int = 0, _vec: int = 0, gram_rows: Optional[int] = None,
+                  _part: int = 0) -> Tensor:
     """One coordinate-descent pass over the rank on ``factors[mode]`` (contiguous fp32 ``[dim_mode, R]`` on the ROCm device), in
     place, over the stored entries of ``T`` alone -- the half-step of ``NTF.fit(solver='ccd')``.  With
     ``q_e,k = fp32(Pa[a_e, k] Pb[b_e, k])`` from the rows of the other two factors an entry names, every owner row with entries runs
@@ -589,7 +656,17 @@ def ntf_ccd_sweep(T, factors: Sequence[Tensor], mode: int, l1: float = 0.0, l2: 
 
     ``_limit`` / ``_order`` / ``_wg_rows`` are ``ccd.ccd_sweep``'s, for the tests and the benchmark; ``_vec``: 0 -- the library's
     rule, 1 -- 4-byte loads of the panel values, 2 -- the rank in groups of four with 16-byte loads where ``R % 4 == 0``.  A
-    row's bits depend on none of ``_limit``, ``_order`` and ``_vec``; ``_wg_rows`` moves rows between two summation orders."""
+    row's bits depend on none of ``_limit``, ``_order`` and ``_vec``; ``_wg_rows`` moves rows between two summation orders.
+
+    ``gram_rows``: None (the default: every row through the sweep above) or an integer >= 0 -- the rows with MORE than
+    ``gram_rows`` stored entries are updated through their own normal equations instead (``nmfmu_sp_ntf_ccd_gram``,
+    csrc/nmfmu_sparse_ntf_ccd_gram.hip): ``Q = sum_e q_e q_e^T`` and ``b = sum_e v_e q_e`` on an exact-fp32 MFMA kernel that cuts
+    a row into parts across the whole device, then ``f_k = max(eps, (b_k - l1 - sum_(j != k) f_j Q[j, k]) / (Q[k, k] + l2 + eps))``
+    for k = 0 .. R-1 -- the same coordinate minimiser at ``O(count R^2)`` instead of ``O(count R)`` work, for rows far longer
+    than the rank that would otherwise keep one workgroup busy alone.  Those rows get OTHER BITS than the sweep's (another
+    summation order; the same minimiser within the bound of DESIGN.md section 41); the rows at or below ``gram_rows`` keep the
+    sweep's bits, and 0 sends every row with entries through the normal equations.  ``_part``: entries per part for the tests
+    and the benchmark, a multiple of 32; 0 -- the library's rule."""
     what = 'ntf_ccd_sweep'
     if mode not in (0, 1, 2):
         raise ValueError(f'{what}: mode must be 0, 1 or 2, got {mode!r}')
@@ -598,6 +675,7 @@ def ntf_ccd_sweep(T, factors: Sequence[Tensor], mode: int, l1: float = 0.0, l2: 
     factors = list(factors)
     if len(factors) != 3 or not all(isinstance(f, Tensor) for f in factors):
         raise ValueError(f'{what}: factors must be three tensors [dim_n, R]')
+    _check_gram_rows(gram_rows, what)
     names = ('factors[0]', 'factors[1]', 'factors[2]')
     for t, name in (*zip(factors, names), (T, 'T')):
         if t.device.type != 'cuda':
@@ -621,6 +699,8 @@ def ntf_ccd_sweep(T, factors: Sequence[Tensor], mode: int, l1: float = 0.0, l2: 
         raise ValueError(f'{what}: _wg_rows must be >= 0, got {_wg_rows!r}')
     if int(_vec) not in (0, 1, 2):
         raise ValueError(f'{what}: _vec must be 0, 1 or 2, got {_vec!r}')
+    if int(_part) < 0 or int(_part) % 32:
+        raise ValueError(f'{what}: _part must be 0 or a positive multiple of 32, got {_part!r}')
     if R > MAX_RANK:
         raise NotImplementedError(f'{what}: rank {R} > {MAX_RANK}, the limit of the sparse kernels')
     if R == 0:
@@ -636,6 +716,15 @@ def ntf_ccd_sweep(T, factors: Sequence[Tensor], mode: int, l1: float = 0.0, l2: 
         if order.dim() != 1 or not torch.equal(torch.sort(order.long())[0], torch.arange(F.shape[0], device=F.device)):
             raise ValueError(f'{what}: _order must be a permutation of the {F.shape[0]} rows of mode {mode}')
     fs = [f.detach() if n == mode else f.detach().contiguous() for n, f in enumerate(factors)]
+    if gram_rows is not None:
+        plan = _gram_plan(T, int(mode), gram_rows, int(_part), R)
+        if plan['batches']:
+            ws = torch.empty(plan['ws'], dtype=torch.float32, device=F.device)
+            _gram_call(T, fs, int(mode), float(l1), float(l2), plan, ws, int(_vec))
+        # the sweep takes the other rows, in the order it was given
+        order = plan['rest'] if _order is None else order[torch.diff(T.modes[mode]['rowptr'])[order.long()] <= gram_rows]
+        if order.numel() == 0:
+            return F
     scratch = torch.empty(max(T.nnz, 4), dtype=torch.float32, device=F.device)
     _ccd_call(T, fs, int(mode), float(l1), float(l2), order, scratch, int(_limit), int(_wg_rows), int(_vec))
     return F
@@ -649,10 +738,17 @@ class _CcdNtf:
     beta = 2 'missing' terms, float64 dots -- each of the t trainable factors times ``a^(1/t)`` (skipped unless a is finite and
     positive), then clamped to >= eps."""
 
-    def __init__(self, T: SparseNtfTarget, fs, train, l1: float, l2: float):
+    def __init__(self, T: SparseNtfTarget, fs, train, l1: float, l2: float, gram_rows: Optional[int] = None):
         self.T, self.fs, self.train, self.l1, self.l2 = T, fs, [bool(t) for t in train], float(l1), float(l2)
         self.rank = fs[0].shape[1]
         self.orders = [_ccd_order(m) if on and T.nnz else None for m, on in zip(T.modes, self.train)]
+        # gram_rows: the rows above it go through their normal equations (_gram_plan), the sweep keeps the rest
+        self.plans = [None] * 3
+        if gram_rows is not None and self.rank:
+            self.plans = [_gram_plan(T, n, gram_rows, 0, self.rank) if o is not None else None for n, o in enumerate(self.orders)]
+            self.orders = [p['rest'] if p is not None else None for p in self.plans]
+            self.ws = torch.empty(max(1, *(p['ws'] for p in self.plans if p is not None), 1), dtype=torch.float32,
+                                  device=T.device)                                          # one for the three modes
         self.scratch = torch.empty(max(T.nnz, 4), dtype=torch.float32, device=T.device)      # one for the three modes
         self.part = torch.empty((T.modes[0]['seg'].shape[0] + 3) // 4, dtype=torch.float64, device=T.device)
         self.out = torch.zeros(1, dtype=torch.float64, device=T.device)
@@ -681,7 +777,9 @@ class _CcdNtf:
         if not self.train[mode]:
             return
         self._ensure_scaled()
-        if self.orders[mode] is not None:
+        if self.plans[mode] is not None and self.plans[mode]['batches']:
+            _gram_call(self.T, self.fs, mode, self.l1, self.l2, self.plans[mode], self.ws)
+        if self.orders[mode] is not None and self.orders[mode].numel():
             _ccd_call(self.T, self.fs, mode, self.l1, self.l2, self.orders[mode], self.scratch)
 
     def divergence(self) -> float:
@@ -725,7 +823,7 @@ class NTF(nn.Module):
 
     def fit(self, V: Tensor, beta: float = 1, tol: float = 1e-4, max_iter: int = 200, verbose: bool = False, alpha: float = 0,
             l1_ratio: float = 0, weights=None, unstored: Optional[str] = None, tile: Optional[str] = None,
-            solver: str = 'mu', precision: str = 'fp32') -> int:
+            solver: str = 'mu', precision: str = 'fp32', gram_rows: Optional[int] = None) -> int:
         """Fit the trainable factors to ``V`` by multiplicative updates: one iteration updates modes 0, 1, 2 in that order.
         Loss checkpoints and the stop rule are ``NMF.fit``'s (after iterations 9, 19, ...: stop when
         ``(previous - loss) / loss_init < tol``); returns the number of iterations.  ``weights``: None, or a dense tensor of
@@ -749,7 +847,11 @@ class NTF(nn.Module):
         descent for a sparse target with ``unstored='missing'`` (beta = 2, no weights), where every owner row has its own
         quadratic: a half-step is one sweep over the stored entries with a maintained residual (``ntf_ccd_sweep``), at the
         order of one multiplicative half-step; the same once-only scale and clamp, over the stored entries.  A dense target
-        or ``unstored='zero'`` has ``solver='hals'``.
+        or ``unstored='zero'`` has ``solver='hals'``.  ``gram_rows`` (``solver='ccd'`` only; None, the default, or an integer
+        >= 0): the owner rows with more than ``gram_rows`` stored entries are updated through their own normal equations on
+        an MFMA kernel that spreads a row over the whole device (``ntf_ccd_sweep(gram_rows=)``) -- for a mode of few, long rows
+        (a context or channel mode), which the sweep leaves to as many workgroups as it has rows.  Those rows get other bits
+        than the sweep's, the same minimiser; the other rows and the default are unchanged bit for bit.
 
         ``precision``: 'fp32' (exact fp32, the default) or 'bf16x3' -- ``solver='hals'`` on a dense target only: every MTTKRP
         of the fit (all modes, the initial scale's and the loss's) runs on the split-bf16 kernel (``ntf_mttkrp(...,
@@ -777,6 +879,9 @@ class NTF(nn.Module):
             if unstored == 'missing':
                 raise NotImplementedError("solver='hals' cannot read unstored entries as missing: every owner row would "
                                           "need its own Gram matrix; use solver='mu' or solver='ccd'")
+        _check_gram_rows(gram_rows, 'NTF.fit')
+        if gram_rows is not None and solver != 'ccd':
+            raise NotImplementedError(f"gram_rows= is the normal-equations route of solver='ccd'; solver={solver!r} has none")
         _check_precision(precision)
         if precision != 'fp32':
             if solver != 'hals':
@@ -788,7 +893,8 @@ class NTF(nn.Module):
         if unstored is not None:
             if tile is not None:
                 raise NotImplementedError('tile= chooses between the dense kernels; a sparse target has one kernel')
-            return self._fit_sparse(V, float(beta), tol, max_iter, verbose, alpha, l1_ratio, weights, unstored, solver)
+            return self._fit_sparse(V, float(beta), tol, max_iter, verbose, alpha, l1_ratio, weights, unstored, solver,
+                                    gram_rows)
         if not isinstance(V, Tensor):
             raise ValueError(f'NTF.fit takes a dense 3-D tensor, got {type(V).__name__}')
         if V.is_sparse:
@@ -815,7 +921,7 @@ class NTF(nn.Module):
                 f.data = f.data.float().contiguous()
             try:
                 return self.fit(V, beta, tol, max_iter, verbose, alpha, l1_ratio, weights, tile=tile, solver=solver,
-                                precision=precision)
+                                precision=precision, gram_rows=gram_rows)
             finally:
                 for f, k in zip(self.factors, keep):
                     f32, f.data = f.data, k
@@ -872,7 +978,8 @@ class NTF(nn.Module):
                 pbar.close()
         return n_iter + 1
 
-    def _fit_sparse(self, V, beta, tol, max_iter, verbose, alpha, l1_ratio, weights, unstored, solver='mu') -> int:
+    def _fit_sparse(self, V, beta, tol, max_iter, verbose, alpha, l1_ratio, weights, unstored, solver='mu',
+                    gram_rows=None) -> int:
         """``fit`` on a sparse target: the refusals in their order, then ``fit``'s loop on ``nmfmu_sp_ntf_step``."""
         if unstored not in ('zero', 'missing'):
             raise ValueError(f"unstored must be 'zero' or 'missing', got {unstored!r}")
@@ -890,7 +997,8 @@ class NTF(nn.Module):
             for f in self.factors:
                 f.data = f.data.float().contiguous()
             try:
-                return self._fit_sparse(V, beta, tol, max_iter, verbose, alpha, l1_ratio, weights, unstored, solver)
+                return self._fit_sparse(V, beta, tol, max_iter, verbose, alpha, l1_ratio, weights, unstored, solver,
+                                        gram_rows)
             finally:
                 for f, k in zip(self.factors, keep):
                     f32, f.data = f.data, k
@@ -909,7 +1017,7 @@ class NTF(nn.Module):
             eng = _HalsNtf(T, fs, [f.requires_grad for f in self.factors], step[0], step[1])
             divergence, half_step = eng.divergence, eng.half_step
         elif solver == 'ccd':
-            eng = _CcdNtf(T, fs, [f.requires_grad for f in self.factors], step[0], step[1])
+            eng = _CcdNtf(T, fs, [f.requires_grad for f in self.factors], step[0], step[1], gram_rows)
             divergence, half_step = eng.divergence, eng.half_step
         else:
             lib = _capi.load()
